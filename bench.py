@@ -2,8 +2,8 @@
 """bench.py -- nnz(C)/s of R-MAT A*A through the MI355X 2D-SUMMA SpGEMM path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--phases P]
-                  [--algo doublebuff|synch] [--exec panel|staged] [--no-cpu-baseline]
-                  [--values rmat|random] [--no-f64-leg] [--grid RxC]
+                  [--algo doublebuff|synch] [--exec panel|staged] [--values rmat|random]
+                  [--grid RxC] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-f64-leg]]
 
 One step = one complete Mult_AnXBn_DoubleBuff (reference ParFriends.h:798-997)
 of Graph500 R-MAT A (SEED 0xDECAFBAD, ef 16, duplicates summed, loops removed)
@@ -17,10 +17,19 @@ torch.distributed.run, one rank per GPU, RCCL row/column communicators (grids
 2x1, 2x2, 4x2 for 2/4/8: DESIGN.md section 6 gives the measured reason; --grid
 1x2 / 2x4 runs BASELINE.md's shapes); an RCCL grid that cannot be created ends
 the run non-zero (CBG_ALLOW_HOST_TRANSPORT=1 opts into the TCP host transport).
-After the headline loop the same structure is timed again with f64 values
-(f64_values / roofline.frac_f64_values): R-MAT's integer values let the slab
-kernels read A as exact f32, real-valued matrices do not.  --scale 18 gives
-configs[1] (C resident on one GPU).
+--scale 18 gives configs[1] (C resident on one GPU).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what takes runs of its own: the copy-bandwidth probes behind
+roofline.peak_measured, a second timed loop on the same structure with f64
+values (f64_values / roofline.frac_f64_values: R-MAT's integer values let the
+slab kernels read A as exact f32, real-valued matrices do not; --no-f64-leg
+skips it) and the CPU baselines (--no-cpu-baseline skips them).
+
+--dump-outputs DIR writes, after the timed steps, a fixed sample of the C the
+last timed step handed its caller as DIR/<name>.npy (OutputSample below); the
+inputs are the same in every run with the same arguments, so two builds can be
+compared array for array.
 
 Prints ONE JSON line on rank 0 (see the driver contract in DESIGN.md).
 """
@@ -73,12 +82,20 @@ def parse():
     p.add_argument("--values", choices=["rmat", "random"], default="rmat",
                    help="rmat: the generator's duplicate counts (small integers); random: U[-1,1) from a hash of "
                         "(row, col) on the same structure (SURVEY 8(d)'s fp variant; A's values are then f64)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the copy-bandwidth probes "
+                        "(roofline.peak_measured), the f64-valued leg and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write a fixed sample of the last timed step's C as DIR/<name>.npy (float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     p.add_argument("--no-f64-leg", dest="f64_leg", action="store_false",
-                   help="skip the second timed loop with f64 (random) values on the same structure")
+                   help="with --full: skip the second timed loop with f64 (random) values on the same structure")
     p.add_argument("--cpu-threads", type=int, default=0, help="default: the CPUs this job may use")
     p.add_argument("--cpu-scale", type=int, default=20, help="scale of the CPU-baseline sample (reference Synch)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def host_cores():
@@ -284,6 +301,84 @@ def f64_values_leg(cbg, grid, A, B, a, step, N):
             "achieved": roof["achieved"], "frac": roof["frac"], "ms_avg": ms_ranks[roof["slowest_rank"]]}
 
 
+class OutputSample:
+    """--dump-outputs: a fixed sample of the C tiles the timed path hands its caller.
+
+    C of the metric's scale is 297 GB, so the files hold a sample: BLOCKS runs of
+    BLOCK_COLS consecutive nonzero columns, counted over the rank's C from its first
+    column on (so the sample does not depend on where the phases cut), one run per
+    1/BLOCKS of the nonzero columns of the rank's B (C has no others) at a seeded
+    position, and of each run the first BLOCK_CAP entries (at most
+    16 * 32768 * 16 B = 8.4 MB; reading it adds 11-16 ms to the last timed step,
+    which the median ms_per_step of three or more steps does not see).  Arrays, all float64:
+      sample_cols     global column of every sampled column
+      sample_col_nnz  its complete entry count in C
+      sample_ptr      start of its kept entries in sample_rows / sample_vals (one more at the end)
+      sample_rows     global rows of the kept entries, sample_vals their values
+      totals          [nnz(C) over all ranks, this rank's nonzero columns, flops over all ranks]
+    The copies are small device-to-host reads of the tile's own arrays through
+    cbg_tile_download views, made while the phase's C is resident (the last timed
+    step's phase callbacks, or the resident C after the loop)."""
+    BLOCKS, BLOCK_COLS, BLOCK_CAP, SEED = 16, 128, 32768, 0x0DD5EED
+
+    def __init__(self, nzc):
+        import numpy as np
+        stride = max(nzc // self.BLOCKS, self.BLOCK_COLS)
+        jitter = np.random.default_rng(self.SEED).integers(0, stride - self.BLOCK_COLS + 1, self.BLOCKS)
+        self.starts = [i * stride + int(j) for i, j in enumerate(jitter)]
+        self.room = [self.BLOCK_CAP] * self.BLOCKS
+        self.seen = 0  # nonzero columns of the tiles taken so far
+        self.cols, self.col_nnz, self.kept, self.rows, self.vals = [], [], [], [], []
+
+    @staticmethod
+    def _download(cbg, c, first_col, ncols, first_entry, nentries):
+        """columns [first_col, +ncols) of device tile c: (cp, jc); or entries
+        [first_entry, +nentries): (ir, val)"""
+        import ctypes
+        import numpy as np
+        cp = np.empty(ncols + 1, np.int64)
+        jc = np.empty(max(ncols, 1), np.int32)
+        ir = np.empty(max(nentries, 1), np.int32)
+        val = np.empty(max(nentries, 1), np.float64)
+        view = cbg.CTile(c.m, c.n, nentries, ncols, c.cp + 8 * first_col, c.jc + 4 * first_col,
+                         c.ir + 4 * first_entry, c.val + 8 * first_entry, 1, 0)
+        host = cbg.CTile(0, 0, 0, 0, cp.ctypes.data, jc.ctypes.data, ir.ctypes.data, val.ctypes.data, 0, 0)
+        cbg._check(cbg.lib().cbg_tile_download(ctypes.byref(view), ctypes.byref(host)))
+        return (cp, jc[:ncols]) if ncols else (ir[:nentries], val[:nentries])
+
+    def take(self, cbg, row_off, col_off, t):
+        """sample device tile t, whose columns follow those of the tiles taken before"""
+        import numpy as np
+        c = t.c
+        for i, s in enumerate(self.starts):
+            lo, hi = max(s, self.seen) - self.seen, min(s + self.BLOCK_COLS, self.seen + c.nzc) - self.seen
+            if lo >= hi or c.nnz == 0:
+                continue
+            cp, jc = self._download(cbg, c, lo, hi - lo, 0, 0)
+            p0 = int(cp[0])
+            n = min(int(cp[-1]) - p0, self.room[i])
+            self.room[i] -= n
+            self.cols.append(jc.astype(np.float64) + col_off)
+            self.col_nnz.append(np.diff(cp).astype(np.float64))
+            self.kept.append(np.diff(np.clip(cp - p0, 0, n)).astype(np.float64))
+            if n:
+                ir, val = self._download(cbg, c, lo, 0, p0, n)
+                self.rows.append(ir.astype(np.float64) + row_off)
+                self.vals.append(val)
+        self.seen += c.nzc
+
+    def save(self, path, suffix, totals):
+        import numpy as np
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)  # noqa: E731
+        os.makedirs(path, exist_ok=True)
+        arrays = {"sample_cols": cat(self.cols), "sample_col_nnz": cat(self.col_nnz),
+                  "sample_ptr": np.concatenate([np.zeros(1), np.cumsum(cat(self.kept))]),
+                  "sample_rows": cat(self.rows), "sample_vals": cat(self.vals),
+                  "totals": np.array(totals)}
+        for name, arr in arrays.items():
+            np.save(os.path.join(path, name + suffix + ".npy"), np.asarray(arr, np.float64))
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -360,6 +455,10 @@ def main():
     exec_mode = cbg.EXEC_PANEL if a.exec_mode == "panel" else cbg.EXEC_STAGED
 
     algo = cbg.DOUBLEBUFF if a.algo == "doublebuff" else cbg.SYNCH
+    sample = OutputSample(B.tile.nzc) if a.dump_outputs else None
+    sample_r0 = cbg.block_range(1 << scale, grid.grid_rows, grid.prow)[0]
+    sample_c0 = cbg.block_range(1 << scale, grid.grid_cols, grid.pcol)[0]
+    sampling = [False]  # set for the last timed step
 
     def step():
         """one complete multiply; returns (local nnz(C), resident C or None)"""
@@ -372,6 +471,8 @@ def main():
             seen[0] += t.nnz
             if a.phase_consumer == "digest":
                 t.digest(0, off)
+            if sampling[0]:
+                sample.take(cbg, sample_r0, sample_c0 + off, t)
 
         cbg.MemEfficientSpGEMM(A, B, a.phases, algo=algo, exec_mode=exec_mode, on_phase=consume)
         plans.append(cbg.phase_plan())
@@ -384,17 +485,18 @@ def main():
         if C is not None:
             C.tile.free()
             C = None
-    # the measured side of the roofline, before the timed region (and again after)
-    peaks = [cbg.hbm_copy_bandwidth(4 << 30, 10) for _ in range(2)] if rank == 0 else []
+    # --full: the measured side of the roofline, before the timed region (and again after)
+    peaks = [cbg.hbm_copy_bandwidth(4 << 30, 10) for _ in range(2)] if rank == 0 and a.full else []
     # K steps, each bracketed by barrier + synchronize and timed as the max over
     # ranks; the whole loop is bracketed the same way (the driver contract)
     ms_local, step_s, pipe = [], [], []
     grid.barrier()
     cbg.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for k in range(a.steps):
         if C is not None:
             C.tile.free()
+        sampling[0] = sample is not None and k == a.steps - 1
         grid.barrier()
         ts = time.perf_counter()
         nnz_local, C = step()
@@ -424,8 +526,13 @@ def main():
     bytes_ranks = [grid.allreduce_sum(bytes_alg if r == rank else 0) for r in range(N)]
     roof = roofline_over_ranks(bytes_ranks, ms_ranks, N, HBM_PEAK_GBS)
     achieved = roof["achieved"]
+    if sample is not None:
+        sampling[0] = False
+        if C is not None:  # resident C of the last timed step
+            sample.take(cbg, sample_r0, sample_c0, C.tile)
+        sample.save(a.dump_outputs, "" if N == 1 else "_rank%d" % rank, [nnz_c, sample.seen, flops])
     f64 = None
-    if a.f64_leg:
+    if a.full and a.f64_leg:
         if C is not None:
             C.tile.free()
             C = None
@@ -436,8 +543,9 @@ def main():
     phases_run = plans[-1]["phases"] if plans else 1
     if rank == 0:
         traffic, traffic_src = pmc_traffic(scale, a.ef, phases_run) if N == 1 and a.values == "rmat" else (None, None)
-        peaks += [cbg.hbm_copy_bandwidth(4 << 30, 10) for _ in range(2)]
-        peak_measured = max(peaks)
+        if a.full:
+            peaks += [cbg.hbm_copy_bandwidth(4 << 30, 10) for _ in range(2)]
+        peak_measured = max(peaks) if peaks else None  # --full only
         out = {
             "metric": "nnz(C)/sec for A·A (R-MAT scale %d) at %d GPUs" % (scale, N),
             "value": nnz_c / med,
@@ -445,6 +553,7 @@ def main():
             "n_gpus": N,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": med * 1e3,
             "higher_is_better": True,
             # every N multiplies the same scale-22 problem (total work fixed)
@@ -495,7 +604,8 @@ def main():
                      else "resident in HBM"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "peak_measured": peak_measured, "frac_measured": achieved / peak_measured,
+                         "peak_measured": peak_measured,
+                         "frac_measured": achieved / peak_measured if peak_measured else None,
                          "peak_measured_method": "16-B/lane device copy of 4 GiB x10 (read+write bytes), "
                                                  "cbg_hbm_copy_bandwidth: the fastest of 8 copy shapes (grid-stride "
                                                  "or one launch streaming the buffer, 1/4/8 loads in flight per "
@@ -512,7 +622,7 @@ def main():
         if f64 is not None:
             out["roofline"]["frac_f64_values"] = f64["frac"]
             out["f64_values"] = f64
-        if N == 1 and not a.no_cpu_baseline:
+        if a.full and N == 1 and not a.no_cpu_baseline:
             # the reference at the metric's own scale (a committed run on the GPU box's
             # host, ~6 min) first; cpu_baseline below is the bounded live sample
             s22 = cpu_baseline_s22()

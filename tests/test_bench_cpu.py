@@ -61,6 +61,109 @@ def test_default_grids_and_flags():
     assert "--no-f64-leg" in src and "frac_f64_values" in src
 
 
+def test_plain_run_flags():
+    """a plain run times the headline only: what takes runs of its own sits behind --full"""
+    b = load_bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        a = b.parse()
+        assert not a.full and a.dump_outputs is None and a.steps == 3
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d", "--no-f64-leg"]
+        a = b.parse()
+        assert a.full and a.dump_outputs == "d" and not a.f64_leg
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            b.parse()
+    finally:
+        sys.argv = argv
+
+
+class _HostTiles:
+    """stands in for the binding: cbg_tile_download copies from host arrays"""
+
+    def __init__(self, cbg):
+        self.CTile = cbg.CTile
+
+    def lib(self):
+        return self
+
+    def _check(self, rc):
+        assert rc == 0
+
+    def cbg_tile_download(self, d, h):
+        import ctypes
+        d, h = d._obj, h._obj
+        assert d.on_device and 0 <= d.nzc <= d.n
+        ctypes.memmove(h.cp, d.cp, 8 * (d.nzc + 1))
+        if d.nzc:
+            ctypes.memmove(h.jc, d.jc, 4 * d.nzc)
+        if d.nnz:
+            ctypes.memmove(h.ir, d.ir, 4 * d.nnz)
+            ctypes.memmove(h.val, d.val, 8 * d.nnz)
+        return 0
+
+
+def test_output_sample_is_independent_of_the_phase_cuts(cbg, tmp_path):
+    """--dump-outputs: the sample of C is the same whether C arrives as one tile or as
+    column phases cut anywhere (a cut inside a sampled run included), holds C's own
+    entries, and keeps at most BLOCK_CAP entries of a run"""
+    import numpy as np
+    b = load_bench()
+    rng = np.random.default_rng(7)
+    m, n = 1000, 4099
+    counts = rng.integers(0, 40, n) * (rng.random(n) < 0.7)  # ~30 % empty columns
+    counts[n // 2:] //= 8  # light columns: their runs stay under the cap
+    cols = {j: np.sort(rng.choice(m, int(k), replace=False)).astype(np.int32) for j, k in enumerate(counts) if k}
+    vals = {j: rng.random(len(r)) for j, r in cols.items()}
+
+    class Tile:  # a DCSC tile of columns [c0, c1), arrays kept alive on the object
+        def __init__(self, c0, c1):
+            js = [j for j in range(c0, c1) if j in cols]
+            self.jc = np.array([j - c0 for j in js] or [0], np.int32)
+            self.cp = np.concatenate([[0], np.cumsum([len(cols[j]) for j in js])]).astype(np.int64)
+            self.ir = np.concatenate([cols[j] for j in js] or [np.zeros(1, np.int32)])
+            self.val = np.concatenate([vals[j] for j in js] or [np.zeros(1)])
+            self.c = cbg.CTile(m, c1 - c0, int(self.cp[-1]), len(js), self.cp.ctypes.data, self.jc.ctypes.data,
+                               self.ir.ctypes.data, self.val.ctypes.data, 1, 0)
+
+    class Sample(b.OutputSample):
+        BLOCKS, BLOCK_COLS, BLOCK_CAP = 8, 16, 200
+
+    fake = _HostTiles(cbg)
+    nz = sorted(cols)
+    starts = Sample(len(nz)).starts
+    assert starts[-1] + Sample.BLOCK_COLS <= len(nz)
+    out = {}
+    for name, cuts in (("one", [0, n]), ("three", [0, nz[starts[0] + 3] + 1, 2500, n]), ("empty", [0, 1, 2, 3000, n])):
+        s = Sample(len(nz))
+        for c0, c1 in zip(cuts[:-1], cuts[1:]):
+            s.take(fake, 100, 2000 + c0, Tile(c0, c1))
+        assert s.seen == len(nz)
+        s.save(str(tmp_path / name), "", [1.0, 2.0, 3.0])
+        out[name] = {f[:-4]: np.load(str(tmp_path / name / f)) for f in sorted(os.listdir(str(tmp_path / name)))}
+    # the same sample from the matrix itself
+    want = {"sample_cols": [], "sample_col_nnz": [], "sample_ptr": [0], "sample_rows": [], "sample_vals": []}
+    capped = 0
+    for st in starts:
+        room = Sample.BLOCK_CAP
+        for j in nz[st:st + Sample.BLOCK_COLS]:
+            k = min(len(cols[j]), room)
+            room -= k
+            want["sample_cols"].append(2000 + j)
+            want["sample_col_nnz"].append(len(cols[j]))
+            want["sample_ptr"].append(want["sample_ptr"][-1] + k)
+            want["sample_rows"] += list(cols[j][:k] + 100)
+            want["sample_vals"] += list(vals[j][:k])
+        capped += room == 0
+    assert 0 < capped < Sample.BLOCKS  # runs cut by the cap and whole runs
+    want["totals"] = [1.0, 2.0, 3.0]
+    for name, got in out.items():
+        assert sorted(got) == sorted(want)
+        for k, v in want.items():
+            assert got[k].dtype == np.float64 and np.array_equal(got[k], np.array(v, np.float64)), (name, k)
+
+
 def test_newest_profile_lookup(tmp_path):
     """the CPU-baseline and traffic records come from the highest round present
     (a hard-coded round list skipped r04)"""

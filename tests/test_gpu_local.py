@@ -1487,7 +1487,12 @@ def _run_tool(path, args, timeout=300):
     exe = os.path.join(repo, *path)
     if not os.path.exists(exe):
         pytest.skip(f"{exe} not built")
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=timeout)
+    # the tools link libcbg.so: name this tree's copy, so that a binary built in another
+    # directory (oracle/_ref/ travels with the tree) runs against the library under test
+    libdir = os.path.join(repo, "combblas-spmm-test_amd")
+    env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(
+        [libdir] + [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p]))
+    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=timeout, env=env)
     return r.returncode, r.stdout + r.stderr
 
 

@@ -8,5 +8,6 @@ tail -5 gpurun_out/gpu_tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 [ -n "$NO_BENCH" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the default line with its f64 leg, measured peak and CPU baselines
 timeout -k 10 400 python bench.py ${BENCH_ARGS} > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || { tail -20 gpurun_out/bench_default.err; exit 1; }
 cat gpurun_out/bench_default.json
