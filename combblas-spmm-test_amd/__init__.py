@@ -389,6 +389,14 @@ def LocalSpGEMM(A, B, sr=PlusTimesSRing, stream=None):
     return LocalHybridSpGEMM(A, B, sr, stream)
 
 
+def LocalSymbolic(A, B, stream=None):
+    """(flops, nnz(C)) of A*B for device tiles without forming C: estimateFLOP +
+    estimateNNZ_Hash (mtSpGEMM.h:1056-1134, 805-933), totals only (cbg_local_symbolic)."""
+    f, n = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().cbg_local_symbolic(ctypes.byref(A.c), ctypes.byref(B.c), ctypes.byref(f), ctypes.byref(n), stream))
+    return f.value, n.value
+
+
 def last_stats():
     f, n, nb, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     a, b = ctypes.c_double(), ctypes.c_double()

@@ -327,7 +327,10 @@ struct Sem;
 template <>
 struct Sem<0> {  // PlusTimesSRing<double,double>
   static __device__ __forceinline__ double mul(double a, double b) { return a * b; }
-  static __device__ __forceinline__ double identity() { return 0.0; }
+  // -0.0, not +0.0: -0.0 + x == x for every x and -0.0 + -0.0 == -0.0, so a slot
+  // whose products are all -0.0 ends as -0.0 in any order, like the reference's
+  // first-insert (mtSpGEMM.h:410-414); from +0.0 it would end as +0.0
+  static __device__ __forceinline__ double identity() { return -0.0; }
   static __device__ __forceinline__ void lds_acc(double* p, double v) { atomicAdd(p, v); }
   static __device__ __forceinline__ double add(double a, double b) { return a + b; }
 };

@@ -3707,12 +3707,15 @@ __global__ void k_vals_f32(int64_t n, const double* __restrict__ v, float* __res
     }
   }
 }
-// Exact integer accumulation (IACC): when every value of A and B is an integer
-// of magnitude <= 2^24 (not -0.0) and every sum the slabs form is bounded below
+// Exact integer accumulation (IACC): when every value of A and B is a NONZERO
+// integer of magnitude <= 2^24 and every sum the slabs form is bounded below
 // 2^31 -- plus-times: max|A| max_j sum_k |B(k,j)| bounds |sum_k a_ik b_kj|;
 // min-plus: max|A| + max|B| -- the slab kernels accumulate in int32 LDS
 // atomics and store the sums as f64: every partial sum is an integer the f64
-// path also holds exactly, so C is the same, bit for bit, in any order.
+// path also holds exactly, so C is the same, bit for bit, in any order.  A zero
+// of either sign in A or B turns it off: 0 * -1 = -0.0, and an entry whose
+// products are all -0.0 is -0.0, which an int cannot carry (nonzero products
+// that cancel give +0.0 on both paths).
 // k_int_bound: out[0] |= 1 if some value is not such an integer, out[1] =
 // max |value|; k_col_int_bound (a wave per column): the same and out[2] = the
 // largest column sum of |values| (capped at INT32_MAX).  (R-MAT scale 22: max
@@ -3746,7 +3749,7 @@ __device__ __forceinline__ void block_int_bound_out(int bad, int mx, int cs, int
 }
 __device__ __forceinline__ bool int_value_bad(double x) {
   const double ax = fabs(x);
-  return !(ax <= 16777216.0) || x != trunc(x) || (x == 0.0 && signbit(x));
+  return !(ax <= 16777216.0) || x != trunc(x) || x == 0.0;
 }
 // fail fast: a wave that sees a bad value raises out[0] at once (one store per
 // wave), and every wave stops at its next check once it is up; k_int_bound

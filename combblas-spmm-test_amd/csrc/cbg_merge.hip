@@ -54,7 +54,8 @@ static void merge_product(const std::vector<cbg_tile>& live, int64_t m, int64_t 
   tile_concat_cols(live, off, m, (int64_t)P * n, Acat.t, s);
   tile_alloc_device(Id.t, (int64_t)P * n, n, (int64_t)P * n, n);
   hipLaunchKernelGGL(k_identity_stack, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, n, P,
-                     semiring == CBG_MIN_PLUS ? 0.0 : 1.0, Id.t.cp, Id.t.jc, Id.t.ir, Id.t.val);
+                     // min-plus unit -0.0: x + -0.0 == x for every x, x = -0.0 too (+0.0 flips its sign)
+                     semiring == CBG_MIN_PLUS ? -0.0 : 1.0, Id.t.cp, Id.t.jc, Id.t.ir, Id.t.val);
   // a merge is not SpGEMM work: keep it out of the multiply statistics
   const LocalStats saved = thread_stats();
   LocalStats mine;

@@ -46,7 +46,7 @@ def save_npz(name, t):
     np.savez_compressed(os.path.join(HERE, name), m=t["m"], n=t["n"], cp=t["cp"], jc=t["jc"], ir=t["ir"], val=t["val"])
 
 
-def run(args, nprocs=1, env=None):
+def run(args, nprocs=1, env=None, parse=True):
     cmd = [DRIVER] + args
     if nprocs > 1:
         cmd = [MPIRUN, "-n", str(nprocs)] + cmd
@@ -56,6 +56,8 @@ def run(args, nprocs=1, env=None):
         e.update(env)
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, env=e).stdout
     recs = []
+    if not parse:  # (a digest of non-finite values prints vsum as nan: not JSON)
+        return recs
     for line in out.splitlines():
         line = line.strip()
         if line.startswith("{"):
@@ -188,7 +190,50 @@ def multtest_fixture():
             f.write(f"{int(r) + 1} {int(c) + 1} {float(v)!r}\n")
 
 
+def write_cbgt(path, t):
+    """a host tile as a 1x1-grid .cbgt (the mirror of read_cbgt)"""
+    nnz, nzc = len(t["ir"]), len(t["jc"])
+    with open(path, "wb") as f:
+        f.write(b"CBGT0001")
+        f.write(np.array([t["m"], t["n"], nnz, nzc, 1, 1, 0, 0, 0, 0], np.int64).tobytes())
+        f.write(np.ascontiguousarray(t["cp"], np.int64).tobytes())
+        f.write(np.ascontiguousarray(t["jc"], np.int32).tobytes())
+        f.write(np.ascontiguousarray(t["ir"], np.int32).tobytes())
+        f.write(np.ascontiguousarray(t["val"], np.float64).tobytes())
+
+
+def special_fixture():
+    """signed zeros, infinities, subnormals, DBL_MAX through the reference's local
+    multiplies: a 60x40 A and a 40x30 B with the f64 palette (plus-times) and the
+    min-plus palette of tests/helpers.py, C by LocalHybridSpGEMM; the heap kernel
+    must give the same bits (NaN by position), or the case is order dependent and
+    no fixture is written."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import assert_tiles_bits_equal, rand_tile, with_palette
+    tmp = tempfile.mkdtemp(prefix="cbg_special_")
+    rng = np.random.default_rng(2024)
+    A0, B0 = rand_tile(rng, 60, 40, 0.3), rand_tile(rng, 40, 30, 0.3)
+    for sr, palette in (("plus", "f64"), ("minplus", "minplus")):
+        A, B = with_palette(A0, B0, palette, rng)
+        pa, pb = os.path.join(tmp, f"{sr}_A.cbgt"), os.path.join(tmp, f"{sr}_B.cbgt")
+        write_cbgt(pa, A)
+        write_cbgt(pb, B)
+        C = {}
+        for algo in ("local", "heap"):
+            pc = os.path.join(tmp, f"{sr}_C_{algo}.cbgt")
+            run(["mult", algo, sr, pa, pb, pc], parse=False)
+            C[algo] = read_cbgt(pc)
+        assert_tiles_bits_equal(C["heap"], C["local"])
+        save_npz(f"special_{sr}_A.npz", A)
+        save_npz(f"special_{sr}_B.npz", B)
+        save_npz(f"special_{sr}_C_local.npz", C["local"])
+        print("special", sr, "nnz(C) =", len(C["local"]["ir"]), flush=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "special":
+        special_fixture()
+        sys.exit(0)
     if len(sys.argv) > 2 and sys.argv[1] == "big":
         # add large-scale symbolic totals to the existing golden.json, e.g. `big 24x16`
         with open(os.path.join(HERE, "golden.json")) as f:

@@ -5,7 +5,9 @@ R-MAT products and within |dc| <= 1e-12 * (|A||B|)_ij for random-valued inputs
 import numpy as np
 import pytest
 
-from helpers import (abs_tile, assert_digest_eq, assert_tiles_equal, digest, golden, load_npz, oracle_local)
+from helpers import (abs_tile, assert_digest_eq, assert_tiles_equal, digest, esc_operands, golden, load_npz,
+                     oracle_local, panel_group_operands as _panel_group_operands, rand_hub_operands,
+                     single_entry_operands, thin_operands)
 
 pytestmark = pytest.mark.gpu
 G = golden()
@@ -69,23 +71,10 @@ def test_bundled_inputs(cbg, name, sr):
         assert_tiles_equal(C, ref)
 
 
-def _rand_tile(rng, m, n, density, lo=-1.0, hi=1.0, hub_cols=()):
-    M = (rng.random((m, n)) < density)
-    for c in hub_cols:
-        M[:, c] = rng.random(m) < 0.8
-    vals = rng.uniform(lo, hi, size=(m, n))
-    cols, rows = np.nonzero(M.T)
-    jc, start = np.unique(cols, return_index=True)
-    return dict(m=m, n=n, cp=np.append(start, len(rows)).astype(np.int64), jc=jc.astype(np.int32),
-                ir=rows.astype(np.int32), val=vals[rows, cols].astype(np.float64))
-
-
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_random_fp_vs_oracle(cbg, seed):
-    rng = np.random.default_rng(seed)
     # hub columns in A and B force the wave, block and big-column (slab) paths
-    Ah = _rand_tile(rng, 3000, 2500, 0.004, hub_cols=(3, 77))
-    Bh = _rand_tile(rng, 2500, 1800, 0.01, hub_cols=(5,))
+    Ah, Bh = rand_hub_operands(seed)
     Bh2 = dict(Bh)
     C = cbg.LocalHybridSpGEMM(cbg.Tile.from_dict(Ah), cbg.Tile.from_dict(Bh)).to_host()
     ref = oracle_local(Ah, Bh2)
@@ -95,22 +84,6 @@ def test_random_fp_vs_oracle(cbg, seed):
     assert_tiles_equal(Cm, oracle_local(Ah, Bh, "minplus"))
 
 
-def _sparse_cols(rng, m, lens, dup_rows=None):
-    """DCSC with column j holding lens[j] distinct sorted random rows (0 = empty column dropped)"""
-    cols, rows = [], []
-    for j, L in enumerate(lens):
-        if L == 0:
-            continue
-        r = np.sort(rng.choice(m if dup_rows is None else dup_rows, L, replace=False))
-        cols.append(np.full(L, j))
-        rows.append(r)
-    cols = np.concatenate(cols)
-    rows = np.concatenate(rows)
-    jc, start = np.unique(cols, return_index=True)
-    return dict(m=m, n=len(lens), cp=np.append(start, len(rows)).astype(np.int64), jc=jc.astype(np.int32),
-                ir=rows.astype(np.int32), val=rng.uniform(-1.0, 1.0, len(rows)))
-
-
 @pytest.mark.parametrize("m", [5000, (1 << 27) + 5])
 def test_small_column_esc(cbg, m):
     # columns of <= 512 products run through the expand-sort-compress waves
@@ -118,31 +91,7 @@ def test_small_column_esc(cbg, m):
     # concentrated on few values force duplicate keys inside a wave, B columns
     # of many entries on empty A columns force several staging rounds, and
     # m >= 2^27 leaves no room for column bits in the sort key (CPW = 1)
-    rng = np.random.default_rng(5)
-    k = 400
-    hot = np.arange(0, m, max(1, m // 40))[:40]      # 40 row values: many duplicates
-    lensA = rng.integers(0, 9, k)
-    lensA[::7] = 0                                      # empty A columns
-    Ah = _sparse_cols(rng, m, lensA, dup_rows=hot)
-    Ah["n"] = k
-    nB = 3000
-    ir, cp = [], [0]
-    for j in range(nB):
-        target = int(rng.choice([1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 100, 128, 160, 200, 256, 300, 400, 512]))
-        ks, f = [], 0
-        for kk in rng.permutation(k):
-            L = int(lensA[kk])
-            if f + L > target:
-                continue
-            ks.append(kk)
-            f += L
-            if f == target or len(ks) > 200:
-                break
-        ks = sorted(ks) if ks else [int(np.argmax(lensA == 0))]
-        ir.extend(ks)
-        cp.append(len(ir))
-    Bh = dict(m=k, n=nB, cp=np.array(cp, np.int64), jc=np.arange(nB, dtype=np.int32),
-              ir=np.array(ir, np.int32), val=rng.uniform(-1.0, 1.0, len(ir)))
+    Ah, Bh = esc_operands(m)
     C = cbg.LocalHybridSpGEMM(cbg.Tile.from_dict(Ah), cbg.Tile.from_dict(Bh)).to_host()
     bound = oracle_local(abs_tile(Ah), abs_tile(Bh))["val"]
     assert_tiles_equal(C, oracle_local(Ah, Bh), rtol=RTOL, bound=bound)
@@ -156,26 +105,7 @@ def test_thin_big_columns(cbg, sr):
     # flops per B entry 1 < R / 4, so they take the expand-sort-compress pass of
     # cbg_thin.hip instead of R (column, panel) pairs; A's rows come from a small
     # pool so that products collide; a few ordinary big and small columns too
-    rng = np.random.default_rng(21)
-    m, k = (1 << 20) + 37, 120000
-    pool = rng.choice(m, 30000, replace=False)
-    rowsA = rng.choice(pool, k)
-    Ah = dict(m=m, n=k, cp=np.arange(k + 1, dtype=np.int64), jc=np.arange(k, dtype=np.int32),
-              ir=rowsA.astype(np.int32), val=rng.uniform(0.5, 2.0, k))
-    hub = np.sort(rng.choice(m, 20000, replace=False))          # one long A column: a regular big column
-    Ah = dict(m=m, n=k + 1, cp=np.append(Ah["cp"], k + len(hub)).astype(np.int64),
-              jc=np.arange(k + 1, dtype=np.int32), ir=np.concatenate([Ah["ir"], hub]).astype(np.int32),
-              val=np.concatenate([Ah["val"], rng.uniform(0.5, 2.0, len(hub))]))
-    lens = list(rng.integers(4100, 30000, 24)) + list(rng.integers(1, 40, 200))
-    ir, cp = [], [0]
-    for L in lens:
-        ir.extend(np.sort(rng.choice(k, int(L), replace=False)))
-        cp.append(len(ir))
-    ir.extend([0, k])  # the hub column and one short one: a regular big column (one entry alone is a copy)
-    cp.append(len(ir))
-    nB = len(cp) - 1
-    Bh = dict(m=k + 1, n=nB, cp=np.array(cp, np.int64), jc=np.arange(nB, dtype=np.int32),
-              ir=np.array(ir, np.int32), val=rng.uniform(-1.0, 1.0, len(ir)))
+    Ah, Bh = thin_operands()
     C = cbg.LocalHybridSpGEMM(cbg.Tile.from_dict(Ah), cbg.Tile.from_dict(Bh), sr).to_host()
     ref = oracle_local(Ah, Bh, sr)
     if sr == "plus":
@@ -191,31 +121,7 @@ def test_single_entry_columns(cbg, sr):
     k_copy_single_big: no symbolic or hash work): short and hub A columns (above
     the 4096-flop big threshold), zero and negative B values, next to ordinary
     small and big columns; entry by entry against the oracle."""
-    rng = np.random.default_rng(5)
-    m, k = (1 << 19) + 11, 3000
-    lens = np.concatenate([rng.integers(0, 30, k - 6), [5000, 9000, 20000, 70000, 4096, 4097]]).astype(np.int64)
-    ir, cp = [], [0]
-    for L in lens:
-        ir.extend(np.sort(rng.choice(m, int(L), replace=False)))
-        cp.append(len(ir))
-    Ah = dict(m=m, n=k, cp=np.array(cp, np.int64), jc=np.arange(k, dtype=np.int32), ir=np.array(ir, np.int32),
-              val=rng.uniform(-2.0, 2.0, len(ir)))
-    bcols = []
-    for j in range(400):
-        t = j % 4
-        if t == 0:    # one entry: a short A column
-            bcols.append([int(rng.integers(0, k - 6))])
-        elif t == 1:  # one entry: a hub
-            bcols.append([int(k - 6 + rng.integers(0, 6))])
-        elif t == 2:  # a few short ones
-            bcols.append(sorted(rng.choice(k - 6, 5, replace=False).tolist()))
-        else:         # hubs and short ones: a big column
-            bcols.append(sorted(set(rng.choice(k - 6, 3, replace=False).tolist() + [k - 3, k - 2])))
-    cpB = np.cumsum([0] + [len(c) for c in bcols]).astype(np.int64)
-    irB = np.concatenate([np.array(c, np.int32) for c in bcols])
-    valB = rng.uniform(-1.0, 1.0, len(irB))
-    valB[::7] = 0.0  # explicit zero products stay structural entries
-    Bh = dict(m=k, n=len(bcols), cp=cpB, jc=np.arange(len(bcols), dtype=np.int32), ir=irB, val=valB)
+    Ah, Bh = single_entry_operands()
     C = cbg.LocalHybridSpGEMM(cbg.Tile.from_dict(Ah), cbg.Tile.from_dict(Bh), sr).to_host()
     ref = oracle_local(Ah, Bh, sr)
     if sr == "plus":
@@ -271,7 +177,7 @@ def test_slab_value_narrowing(cbg, kind):
 @pytest.mark.parametrize("kind", ["rmat", "negative", "scaled_past_bound", "minus_zero", "half_integer"])
 def test_int_accumulate_paths(cbg, kind):
     """The slab kernels' exact int32 accumulation (IACC) runs when every value of A and
-    B is an integer of magnitude <= 2^24 (not -0.0) and max|A| max_j sum_k |B(k,j)|
+    B is a nonzero integer of magnitude <= 2^24 and max|A| max_j sum_k |B(k,j)|
     < 2^31 (min-plus: max|A| + max|B| < 2^30), else the f64 path; either way C equals
     the oracle's (integer sums are exact in f64 in any order).  R-MAT scale 14 (bitmap
     and rank slabs), both semirings."""
@@ -302,46 +208,6 @@ def test_int_accumulate_paths(cbg, kind):
         else:
             assert on == expect, (kind, sr, w)
         assert_tiles_equal(Ch, oracle_local(Ah, Ah, sr))  # exact: integer (or half-integer) sums
-
-
-def _panel_group_operands(m=(1 << 20) + 77):
-    """Tall A (m = 2^20 + 77: 5 row panels of 2^18, the last one partial) and a B whose
-    columns land in every big-column class: panel groups of 4 and 2 (expected products
-    per group <= 4096), single-panel hash pairs, bitmap pairs, a group with > 512 B
-    entries, and groups whose products crowd into one panel (nnz > one hash slab), which
-    must fall back to per-panel slabs."""
-    rng = np.random.default_rng(11)
-    heavy, light, local = 3000, 1000, 200  # A columns: 100 rows anywhere / 8 rows / 100 rows in panel 0
-
-    def col(nr, hi):
-        return np.sort(rng.choice(hi, nr, replace=False))
-
-    acols = [col(100, m) for _ in range(heavy)] + [col(8, m) for _ in range(light)] + \
-            [col(100, 1 << 18) for _ in range(local)]
-    k = len(acols)
-    cnt = np.array([len(c) for c in acols])
-    Ah = dict(m=m, n=k, cp=np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), jc=np.arange(k, dtype=np.int32),
-              ir=np.concatenate(acols).astype(np.int32),
-              val=rng.integers(1, 5, int(cnt.sum())).astype(np.float64))
-    groups = [(100, 5, 40, 0), (100, 44, 48, 0), (100, 78, 84, 0), (50, 140, 160, 0), (30, 280, 320, 0),
-              (20, 600, 601, 1), (20, 45, 46, 2)]
-    bcols = []
-    for num, lo, hi, kind in groups:
-        for _ in range(num):
-            nb = int(rng.integers(lo, hi))
-            if kind == 0:
-                bcols.append(np.sort(rng.choice(heavy, nb, replace=False)))
-            elif kind == 1:
-                bcols.append(np.sort(heavy + rng.choice(light, nb, replace=False)))
-            else:
-                bcols.append(np.sort(heavy + light + rng.choice(local, nb, replace=False)))
-    n = len(bcols)
-    perm = rng.permutation(n)
-    bcols = [bcols[i] for i in perm]
-    bc = np.array([len(c) for c in bcols])
-    Bh = dict(m=k, n=n, cp=np.concatenate([[0], np.cumsum(bc)]).astype(np.int64), jc=np.arange(n, dtype=np.int32),
-              ir=np.concatenate(bcols).astype(np.int32), val=rng.integers(1, 3, int(bc.sum())).astype(np.float64))
-    return Ah, Bh
 
 
 @pytest.mark.parametrize("sr", ["plus", "minplus"])
