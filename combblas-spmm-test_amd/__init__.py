@@ -412,7 +412,7 @@ WORK_CLASSES = (["bitmap_small_kept", "bitmap_small_mark", "bitmap_large_kept", 
                 ["rank_N%d" % n for n in (1024, 2048, 4096)] +
                 ["sym_panel_units", "sym_group_units", "sym_deferred_units", "esc_columns", "thin_columns",
                  "single_big_entries", "hash_bin_columns", "wave_bin_columns", "int_accumulate"] +
-                ["group_rank_N%d" % n for n in (2048, 4096)])
+                ["group_rank_N%d" % n for n in (2048, 4096)] + ["big_cut_flops"])
 
 
 def last_work_stats():

@@ -263,16 +263,24 @@ constexpr int64_t THIN_RATIO = 4;
 // copy1: a column with one B entry and 0 < flops <= big is C(:,j) = A(:,k) * b,
 // nnz = flops: mode 0 writes cnt and bins it with the empty columns, mode 1
 // skips it (k_copy_single writes it)
+// low (mode 0, 0 = off): the lower big-column cut the host may still choose once it has
+// the histogram (BinRemap).  For the columns of low < flops <= big, lo_stats gets their B
+// entries ([0] the ones that stay big, [1] the ones the lower cut makes thin) and the thin
+// ones' count and flops ([2], [3]); a thin one's bin byte carries BIN_THIN_LOW.
+constexpr int BIN_THIN_LOW = 0x80;
 __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __restrict__ flops,
                                                   int32_t* __restrict__ cnt, int mode, int copy1, int64_t big, BinThr thr,
                                                   uint8_t* __restrict__ bin, int* __restrict__ hist,
                                                   int64_t fused_max, const int64_t* __restrict__ cpB, int big_bin,
                                                   unsigned long long* __restrict__ big_entries,
                                                   unsigned long long* __restrict__ bin_flops, int thin_R,
-                                                  int thin_bin) {
+                                                  int thin_bin, int64_t low,
+                                                  unsigned long long* __restrict__ lo_stats) {
   __shared__ int lh[MAXBINS];
   __shared__ unsigned long long lf[MAXBINS];
   __shared__ unsigned long long lbe, lbt;
+  __shared__ unsigned long long llo[4];
+  if (threadIdx.x < 4) llo[threadIdx.x] = 0;
   if (threadIdx.x < MAXBINS) {
     lh[threadIdx.x] = 0;
     lf[threadIdx.x] = 0;
@@ -280,6 +288,7 @@ __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __re
   if (threadIdx.x == 0) lbe = lbt = 0;
   __syncthreads();
   unsigned long long be = 0, bt = 0;
+  unsigned long long lo_e = 0, lo_t = 0, lo_n = 0, lo_f = 0;
   const int64_t i0 = blockIdx.x * (int64_t)(256 * BIN_ITEMS) + threadIdx.x;
 #pragma unroll 4
   for (int j = 0; j < BIN_ITEMS; ++j) {
@@ -303,7 +312,19 @@ __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __re
         b = 0;
         if (mode == 0) cnt[i] = (int32_t)f;
       }
-      bin[i] = (uint8_t)b;
+      int flag = 0;
+      if (low > 0 && f > low && f <= big && !single) {
+        const unsigned long long ne = (unsigned long long)(cpB[i + 1] - cpB[i]);
+        if (thin_R > 0 && f * THIN_RATIO < (int64_t)ne * (int64_t)thin_R) {
+          flag = BIN_THIN_LOW;
+          lo_t += ne;
+          lo_n += 1;
+          lo_f += (unsigned long long)f;
+        } else {
+          lo_e += ne;
+        }
+      }
+      bin[i] = (uint8_t)(b | flag);
       atomicAdd(&lh[b], 1);
       if (f > 0) atomicAdd(&lf[b], (unsigned long long)f);
       if (big_entries && b >= big_bin) (thin ? bt : be) += (unsigned long long)(cpB[i + 1] - cpB[i]);
@@ -311,25 +332,51 @@ __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __re
   }
   if (big_entries && be) atomicAdd(&lbe, be);
   if (big_entries && bt) atomicAdd(&lbt, bt);
+  if (lo_e) atomicAdd(&llo[0], lo_e);
+  if (lo_t) {
+    atomicAdd(&llo[1], lo_t);
+    atomicAdd(&llo[2], lo_n);
+    atomicAdd(&llo[3], lo_f);
+  }
   __syncthreads();
   if (threadIdx.x < thr.nb && lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
   if (threadIdx.x < thr.nb && lf[threadIdx.x]) atomicAdd(&bin_flops[threadIdx.x], lf[threadIdx.x]);
   if (big_entries && threadIdx.x == 0 && lbe) atomicAdd(big_entries, lbe);
   if (big_entries && threadIdx.x == 0 && lbt) atomicAdd(big_entries + 1, lbt);
+  if (low > 0 && threadIdx.x < 4 && llo[threadIdx.x]) atomicAdd(&lo_stats[threadIdx.x], llo[threadIdx.x]);
 }
 
+// the lower big-column cut, chosen after k_classify ran: the columns of the bins
+// [lo, hi) move to bin `to`, the nthin of them flagged BIN_THIN_LOW to thin_bin
+// (to < 0: no remap; the flag is dropped)
+struct BinRemap {
+  int lo = 0, hi = 0, to = -1, thin_bin = 0, nthin = 0;
+};
 // hist: the bins' counts (their exclusive prefix is each bin's offset in perm);
 // cursor: per-bin fill counters, zero on entry
 __global__ __launch_bounds__(256) void k_bin_scatter(int64_t n, const uint8_t* __restrict__ bin, int nb,
                                                      const int* __restrict__ hist, int* __restrict__ cursor,
-                                                     int32_t* __restrict__ perm) {
-  __shared__ int lc[MAXBINS], lb[MAXBINS], loff[MAXBINS];
-  if (threadIdx.x < MAXBINS) lc[threadIdx.x] = 0;
+                                                     int32_t* __restrict__ perm, BinRemap rm) {
+  __shared__ int lc[MAXBINS], lb[MAXBINS], loff[MAXBINS], lh[MAXBINS];
+  if (threadIdx.x < MAXBINS) {
+    lc[threadIdx.x] = 0;
+    lh[threadIdx.x] = threadIdx.x < nb ? hist[threadIdx.x] : 0;
+  }
+  __syncthreads();
   if (threadIdx.x == 0) {
+    if (rm.to >= 0) {
+      int moved = 0;
+      for (int q = rm.lo; q < rm.hi; ++q) {
+        moved += lh[q];
+        lh[q] = 0;
+      }
+      lh[rm.to] += moved - rm.nthin;
+      lh[rm.thin_bin] += rm.nthin;
+    }
     int a = 0;
     for (int q = 0; q < nb; ++q) {
       loff[q] = a;
-      a += hist[q];
+      a += lh[q];
     }
   }
   __syncthreads();
@@ -338,7 +385,13 @@ __global__ __launch_bounds__(256) void k_bin_scatter(int64_t n, const uint8_t* _
 #pragma unroll
   for (int j = 0; j < BIN_ITEMS; ++j) {
     const int64_t i = i0 + j * 256;
-    b[j] = i < n ? bin[i] : -1;
+    int v = i < n ? bin[i] : -1;
+    if (v >= 0) {
+      const bool thin_low = v & BIN_THIN_LOW;
+      v &= BIN_THIN_LOW - 1;
+      if (rm.to >= 0 && v >= rm.lo && v < rm.hi) v = thin_low ? rm.thin_bin : rm.to;
+    }
+    b[j] = v;
   }
 #pragma unroll
   for (int j = 0; j < BIN_ITEMS; ++j) slot[j] = b[j] >= 0 ? atomicAdd(&lc[b[j]], 1) : 0;
@@ -1320,7 +1373,7 @@ constexpr int SLAB_RANK0 = 2 + SLAB_HASH_NCLS;
 // panel-group slabs of more than grank_min nonzeros spanning <= 2^22 rows
 constexpr int SLAB_GRANK_NCLS = 2;
 constexpr int SLAB_GRANK0 = SLAB_RANK0 + SLAB_RANK_NCLS;
-static_assert(CBG_WORK_GRANK0 == CBG_WORK_IACC + 1 && CBG_WORK_N == CBG_WORK_GRANK0 + SLAB_GRANK_NCLS,
+static_assert(CBG_WORK_GRANK0 == CBG_WORK_IACC + 1 && CBG_WORK_BIG_CUT == CBG_WORK_GRANK0 + SLAB_GRANK_NCLS,
               "cbg_last_work_stats group rank classes");
 constexpr int SLAB_NCLS = 2 + SLAB_HASH_NCLS + SLAB_RANK_NCLS + SLAB_GRANK_NCLS;
 __device__ __forceinline__ int slab_class(const int4& d, int small_cap, int rank_span, int rank_min, int grank_min) {
@@ -1947,6 +2000,17 @@ __global__ __launch_bounds__(256) void k_copy_single_big(int64_t nz, const int64
 #ifndef CBG_ROWS_DIRECT_NT  // ... as nontemporal stores: +66 GB of partial-line writes per scale-22 step
 #define CBG_ROWS_DIRECT_NT 0
 #endif
+// the rank-ordered row copies of the bitmap, rank and group rank slabs under IACC
+// as nontemporal stores like their values: whole lines, coalesced, unlike the
+// bitmap walk's partial lines above (scale 22: 312.0 -> 306.8 ms, three rounds each)
+#ifndef CBG_ROWS_NT
+#define CBG_ROWS_NT 1
+#endif
+template <bool IA, class T>
+__device__ __forceinline__ void st_rows(T* p, T v) {
+  if constexpr (IA && CBG_ROWS_NT) st_emit(p, v);
+  else *p = v;
+}
 template <int CAP, int BS>
 struct SlabLds {
   // vals[CAP] f64 | bv[BS] f64 | bm[SLAB_WORDS] | pref[BS+4] | st[BS] | tmp[BS/64+4] | (pad 16) wpre[SLAB_WORDS] u16
@@ -2242,7 +2306,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       // rows and values in rank order (C's order): coalesced copies
       const int* ivals = reinterpret_cast<const int*>(vals);
       for (int j = tid; j < nout; j += BS) {
-        out_ir[obase + j] = ivals[CAP + j];
+        st_rows<true>(&out_ir[obase + j], ivals[CAP + j]);
         st_stream(&out_val[obase + j], (double)ivals[j]);
       }
     } else if (!(c_dbg & 8) && CBG_ROWS_DIRECT) {
@@ -2839,7 +2903,7 @@ __global__ __launch_bounds__(BS) void k_num_slab_rank(const SlabRec* __restrict_
     if (!(c_dbg & 1024)) {
       const int* rows = reinterpret_cast<const int*>(bm);
       for (int j = tid; j < nout; j += BS) {
-        out_ir[obase + j] = rows[j];
+        st_rows<IA>(&out_ir[obase + j], rows[j]);
         st_emit(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
       }
     }
@@ -3090,7 +3154,7 @@ __global__ __launch_bounds__(BS) void k_num_slab_grank(const SlabRec* __restrict
     {
       const int* rows = reinterpret_cast<const int*>(smem + (L::ROWS_IN_L1 ? L::L1_OFF : L::ROWS_OFF));
       for (int j = tid; j < nout; j += BS) {
-        out_ir[obase + j] = rows[j];
+        st_rows<IA>(&out_ir[obase + j], rows[j]);
         st_emit(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
       }
     }
@@ -3192,20 +3256,37 @@ static void set_lds(K kernel, size_t bytes) {
 #ifndef CBG_SYM_FUSED_LAST
 #define CBG_SYM_FUSED_LAST 9
 #endif
-static const int64_t kSymThr[] = {0, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096};
+static constexpr int64_t kSymThr[] = {0, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096};
 constexpr int SYM_FUSED_LAST = CBG_SYM_FUSED_LAST;
 // columns with more flops than this take the bitmap+rank slab path (runtime
 // override: CBG_BIG_FLOPS); it must stay <= 4096 so that every other column's
 // nnz fits the largest numeric hash bin
-static int64_t big_flops(int64_t m) {
-  static const char* e = getenv("CBG_BIG_FLOPS");
+// *fixed: the override is set (read per call), so local_spgemm_impl's rule for
+// the lower cut stays out
+static int64_t big_flops(int64_t m, bool* fixed) {
+  const char* e = getenv("CBG_BIG_FLOPS");
   // measured on R-MAT (scale 18/20): 4096 once hash slabs take the sparse
   // (column, panel) pairs and the block hash bins emit by bucket sort
   int64_t b = e ? atoll(e) : 4096;
   if (b < 64) b = 64;
   if (b > 4096) b = 4096;
+  *fixed = e != nullptr;
   return b;
 }
+// The lower cut, chosen per multiply once the symbolic bins' flops are on the
+// host (local_spgemm_impl): the columns of LOW_CUT_FLOPS < flops <= 4096
+// (symbolic bins [LOW_CUT_BIN0, LOW_CUT_BIN1), block hash on the side stream)
+// join the big columns as whole-column panel groups, where
+//  (a) such a group fits the group rank slab: m <= 2^GRANK_SPAN_LOG (above it
+//      the groups become hash slabs: scale 24 lost 3 % to a static 1024), and
+//  (b) the columns above 4096 flops carry at least LOW_CUT_NUM / LOW_CUT_DEN of
+//      the multiply's flops, so the panel path's fixed costs (panel maps, slab
+//      lists, their launches) are paid anyway (GalerkinNew, a 6 ms product
+//      with few big columns, lost 17 % to a static 1024).
+constexpr int64_t LOW_CUT_FLOPS = 1024;
+constexpr int LOW_CUT_BIN0 = 11, LOW_CUT_BIN1 = 13;
+constexpr int LOW_CUT_NUM = 1, LOW_CUT_DEN = 2;
+static_assert(kSymThr[LOW_CUT_BIN0 - 1] == LOW_CUT_FLOPS && kSymThr[LOW_CUT_BIN1 - 1] == 4096, "bins of the lower cut");
 // bins of the numeric phase (key = exact nnz, big columns forced to the last bin)
 //  0: 0 | 1: <=32 wave T64 | 2: <=64 wave T128 | 3: <=128 wave T256 | 4: <=256 wave T512 |
 //  5: <=512 block T1024 | 6: <=1024 block T2048 | 7: <=2048 block T4096 | 8: <=4096 block T8192 | 9: big
@@ -3552,6 +3633,8 @@ struct BinPending {
   std::vector<int> h;
   std::vector<unsigned long long> hf;  // flops per bin
   unsigned long long big_entries[2] = {0, 0};  // B entries of the big / thin columns
+  unsigned long long lo_stats[4] = {0, 0, 0, 0};  // k_classify's lo_stats
+  BinRemap remap;
   void read() {
     const int* hi = reinterpret_cast<const int*>(host);
     h.assign(hi, hi + MAXBINS);
@@ -3560,26 +3643,28 @@ struct BinPending {
     big_entries[1] = be[1];
     const unsigned long long* bf = reinterpret_cast<const unsigned long long*>(hi + 2 * MAXBINS + 4);
     hf.assign(bf, bf + MAXBINS);
+    std::memcpy(lo_stats, bf + MAXBINS, sizeof(lo_stats));
   }
 };
+constexpr int BIN_HIST_INTS = 4 * MAXBINS + 4 + 8;  // counts | offsets | big, thin entries | flops per bin | lo_stats
 // cpB/big_bin (mode 0): also count the B entries of the bins >= big_bin into bp.big_entries
 static void bin_classify(int64_t n, const int64_t* flops, int32_t* cnt, int mode, const int64_t* thr,
                          int nthr, int64_t big, BinPending& bp, hipStream_t s, int64_t fused_max = 0,
                          const int64_t* cpB = nullptr, int big_bin = MAXBINS, int thin_R = 0, int thin_bin = 0,
-                         int copy1 = 0) {
+                         int copy1 = 0, int64_t low = 0) {
   bp.bt.nb = nthr + 1;
   for (int i = 0; i < nthr; ++i) bp.bt.t[i] = thr[i];
   bp.bin.reset(n);
-  // counts | offsets | big, thin entries (u64) | flops per bin (u64)
-  bp.hist.reset(2 * MAXBINS + 4 + 2 * MAXBINS);
-  CBG_HIP(hipMemsetAsync(bp.hist.p, 0, sizeof(int) * (4 * MAXBINS + 4), s));
+  // counts | offsets | big, thin entries (u64) | flops per bin (u64) | lo_stats (u64)
+  bp.hist.reset(BIN_HIST_INTS);
+  CBG_HIP(hipMemsetAsync(bp.hist.p, 0, sizeof(int) * BIN_HIST_INTS, s));
   unsigned long long* be = (cpB && mode == 0) ? reinterpret_cast<unsigned long long*>(bp.hist.p + 2 * MAXBINS) : nullptr;
   unsigned long long* bf = reinterpret_cast<unsigned long long*>(bp.hist.p + 2 * MAXBINS + 4);
   hipLaunchKernelGGL(k_classify, dim3(nblk(n, 256 * BIN_ITEMS)), dim3(256), 0, s, n, flops, cnt, mode, copy1, big, bp.bt,
-                     bp.bin.p, bp.hist.p, fused_max, cpB, big_bin, be, bf, thin_R, thin_bin);
-  // one copy of counts | offsets | big entries | flops per bin
+                     bp.bin.p, bp.hist.p, fused_max, cpB, big_bin, be, bf, thin_R, thin_bin, be ? low : 0, bf + MAXBINS);
+  // one copy of counts | offsets | big entries | flops per bin | lo_stats
   bp.host = host_stage(mode == 0 ? STAGE_BINS_SYM : STAGE_BINS_NUM);
-  CBG_HIP(hipMemcpyAsync(bp.host, bp.hist.p, sizeof(int) * (4 * MAXBINS + 4), hipMemcpyDeviceToHost, s));
+  CBG_HIP(hipMemcpyAsync(bp.host, bp.hist.p, sizeof(int) * BIN_HIST_INTS, hipMemcpyDeviceToHost, s));
 }
 static void bin_scatter(int64_t n, BinPending& bp, Binned& out, hipStream_t s, DeferredFree& df) {
   const int nb = bp.bt.nb;
@@ -3593,7 +3678,7 @@ static void bin_scatter(int64_t n, BinPending& bp, Binned& out, hipStream_t s, D
   out.flops = bp.hf;
   out.perm.reset(n);
   hipLaunchKernelGGL(k_bin_scatter, dim3(nblk(n, 256 * BIN_ITEMS)), dim3(256), 0, s, n, bp.bin.p, nb, bp.hist.p,
-                     bp.hist.p + MAXBINS, out.perm.p);
+                     bp.hist.p + MAXBINS, out.perm.p, bp.remap);
   df.take(bp.bin);  // released after the multiply's final synchronization
   df.take(bp.hist);
 }
@@ -3877,6 +3962,7 @@ void local_spgemm(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_tile& 
   t.ms_symbolic += mine.ms_symbolic;
   t.ms_numeric += mine.ms_numeric;
   for (int i = 0; i < CBG_WORK_N; ++i) t.work[i] += mine.work[i];
+  t.work[CBG_WORK_BIG_CUT] = mine.work[CBG_WORK_BIG_CUT];  // a threshold: the last multiply's
   if (st) *st = mine;
 }
 
@@ -3982,7 +4068,8 @@ void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_t
   CBG_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (nz + 1), s));
   // symbolic
   Binned sb;
-  const int64_t big = big_flops(A.m);
+  bool big_fixed = false;
+  int64_t big = big_flops(A.m, &big_fixed);  // (lowered below where the rule takes the lower cut)
   {
     // once per device (c_dbg exists once per device; a pageable copy holds the host ~20 us)
     static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
@@ -4029,17 +4116,60 @@ void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_t
     // thin when flops * THIN_RATIO < B entries * R (1 and 2 measured equal at scales 22/24)
     const int ratio = (int)THIN_RATIO;
     thin_R = (fused && thin_on && bp.R >= 4) ? (int)(bp.R * THIN_RATIO / ratio) : 0;
-    bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, thin_R, THIN_BIN, copy1);
+    // condition (a) of the lower cut; (b) needs the bins' flops
+    const int64_t low = (!big_fixed && big > LOW_CUT_FLOPS && A.m <= (1LL << GRANK_SPAN_LOG)) ? LOW_CUT_FLOPS : 0;
+    bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, thin_R, THIN_BIN, copy1,
+                 low);
     CBG_HIP(hipStreamSynchronize(s));  // host sync 1 of 4: the symbolic bins' sizes
     sp.read();
     if (thin_R && (double)sp.hf[THIN_BIN] * THIN_BYTES_PER_PRODUCT > 0.25 * device_bytes_available()) {
       // the sort's temporaries (64-bit counts, cbg_sort.hip) would take more than a
       // quarter of the device memory left: classify again without thin columns
       thin_R = 0;
-      bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, 0, THIN_BIN, copy1);
+      bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, 0, THIN_BIN, copy1,
+                   low);
       CBG_HIP(hipStreamSynchronize(s));
       sp.read();
     }
+    if (low > 0) {
+      // the lower cut (LOW_CUT_FLOPS above): from here on the multiply runs as under
+      // CBG_BIG_FLOPS=1024 -- the bins' columns move in the scatter (BinRemap), the
+      // host's copy of the histogram moves with them
+      static_assert(GROUP_PRODUCTS >= 4096, "one group class takes every column of the rerouted bins");
+      unsigned long long all_f = 0, big_f = 0;
+      int moved = 0;
+      for (int b = 0; b <= THIN_BIN; ++b) all_f += sp.hf[b];
+      for (int b = NSMALL; b <= THIN_BIN; ++b) big_f += sp.hf[b];
+      for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) moved += sp.h[b];
+      const unsigned long long thin_f = sp.hf[THIN_BIN] + sp.lo_stats[3];
+      const bool thin_fits =
+          !thin_R || !sp.lo_stats[2] || (double)thin_f * THIN_BYTES_PER_PRODUCT <= 0.25 * device_bytes_available();
+      if (moved > 0 && big_f * LOW_CUT_DEN >= all_f * LOW_CUT_NUM && thin_fits) {
+        int to = NSMALL + NGCLS - 1;  // the first group class in use: thr >= GROUP_PRODUCTS >= their flops
+        for (int c = NGCLS - 2; c >= 0; --c)
+          if (thr[NSMALL + c] >= 0) to = NSMALL + c;
+        const int nthin = (int)sp.lo_stats[2];
+        unsigned long long moved_f = 0;
+        for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) {
+          moved_f += sp.hf[b];
+          sp.h[b] = 0;
+          sp.hf[b] = 0;
+        }
+        sp.h[to] += moved - nthin;
+        sp.hf[to] += moved_f - sp.lo_stats[3];
+        sp.h[THIN_BIN] += nthin;
+        sp.hf[THIN_BIN] += sp.lo_stats[3];
+        sp.big_entries[0] += sp.lo_stats[0];
+        sp.big_entries[1] += sp.lo_stats[1];
+        sp.remap.lo = LOW_CUT_BIN0;
+        sp.remap.hi = LOW_CUT_BIN1;
+        sp.remap.to = to;
+        sp.remap.thin_bin = THIN_BIN;
+        sp.remap.nthin = nthin;
+        big = LOW_CUT_FLOPS;
+      }
+    }
+    work[CBG_WORK_BIG_CUT] = big;
     bin_scatter(nz, sp, sb, s, df);
     big_entries = (int64_t)sp.big_entries[0];
     thin_entries = (int64_t)sp.big_entries[1];

@@ -174,7 +174,8 @@ int cbg_last_stats(int64_t* flops, int64_t* nnz, double* ms_symbolic, double* ms
  * columns of the one-pass small-column kernels, thin columns, entries of the
  * single-entry big columns, columns of the numeric hash / wave bins, and the
  * multiplies whose slab kernels accumulated exact integers in int32 (A's and B's
- * values integers of magnitude <= 2^24 whose sums stay below 2^31).
+ * values integers of magnitude <= 2^24 whose sums stay below 2^31), and the flops
+ * above which a column took the big-column path.
  * counts[i] for i < min(n, CBG_WORK_N); returns CBG_WORK_N. */
 enum {
   CBG_WORK_BITMAP_SMALL_KEPT = 0,
@@ -193,7 +194,9 @@ enum {
   CBG_WORK_WAVE_BIN_COLUMNS = 23,
   CBG_WORK_IACC = 24, /* multiplies whose slabs accumulated exact integers in int32 */
   CBG_WORK_GRANK0 = 25, /* + k: panel-group rank slabs of <= 2048, 4096 nonzeros */
-  CBG_WORK_N = 27
+  CBG_WORK_BIG_CUT = 27, /* the big-column cut in flops (4096, or 1024 where the multiply's rule or
+                          * CBG_BIG_FLOPS lowered it): not summed, the call's last multiply's */
+  CBG_WORK_N = 28
 };
 int cbg_last_work_stats(int64_t* counts, int n);
 /* last call's multiway merges (MergeAll / MultiwayMerge): partial entries in,
