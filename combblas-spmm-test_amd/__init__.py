@@ -60,6 +60,12 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, cty
                                 ctypes.c_size_t)
 
 
+class CMclParams(ctypes.Structure):
+    """cbg_mcl_params: hardThreshold, selectNum, recoverNum, recoverPct of MCLPruneRecoverySelect"""
+    _fields_ = [("hard_threshold", ctypes.c_double), ("select_num", ctypes.c_int64), ("recover_num", ctypes.c_int64),
+                ("recover_pct", ctypes.c_double)]
+
+
 class CHostComm(ctypes.Structure):
     _fields_ = [("bcast", BCAST_FN), ("allgather", ALLGATHER_FN), ("user", ctypes.c_void_p)]
 
@@ -77,6 +83,8 @@ EXPORTS = [
     "cbg_tile_concat_cols", "cbg_device_memory", "cbg_last_summa_info", "cbg_summa_spgemm_memeff",
     "cbg_last_summa_comm",
     "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_store_probe",
+    "cbg_tile_col_stats", "cbg_tile_prune_column", "cbg_grid_kselect", "cbg_grid_mcl_prune", "cbg_summa_spgemm_mcl",
+    "cbg_mcl_kselect_bounds", "cbg_last_mcl_stats",
 ]
 Column, Row = 0, 1  # DimApply dimensions (SpDefs.h Dim)
 OP_MULTIPLIES, OP_PLUS, OP_MIN, OP_MAX = 0, 1, 2, 3
@@ -152,6 +160,14 @@ def lib():
         "cbg_last_summa_info": ([ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_last_summa_comm": ([ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_tile_col_stats": ([T, vp, i32, vp, vp], i32),
+        "cbg_tile_prune_column": ([T, vp, T], i32),
+        "cbg_grid_kselect": ([vp, T, vp, i64, i64, vp], i32),
+        "cbg_grid_mcl_prune": ([vp, T, ctypes.POINTER(CMclParams), T], i32),
+        "cbg_summa_spgemm_mcl": ([vp, T, T, i64, i64, i32, i32, i32, i32, i64, PHASE_FN, vp, T,
+                                  ctypes.POINTER(CMclParams)], i32),
+        "cbg_mcl_kselect_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_last_mcl_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
     }
     experiment = "CBG_LIB" in os.environ  # an older build under A/B may lack the newest entry points
     for name, (args, res) in sig.items():
@@ -253,6 +269,22 @@ class Tile:
         random-valued inputs; the tile's global offsets make it grid-independent); in place."""
         _check(lib().cbg_tile_random_values(ctypes.byref(self.c), seed, int(row_off), int(col_off)))
         return self
+
+    def col_stats(self, thr, strict):
+        """(cnt, sum) of the values of every local column kept under thr[column]
+        (strict: v > thr, else !(v < thr)); thr: one value or n of them."""
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, np.float64), (self.n,)))
+        cnt, tot = np.zeros(self.n, np.int64), np.zeros(self.n, np.float64)
+        _check(lib().cbg_tile_col_stats(ctypes.byref(self.c), thr.ctypes.data, int(bool(strict)), cnt.ctypes.data,
+                                        tot.ctypes.data))
+        return cnt, tot
+
+    def prune_column(self, thr):
+        """SpParMat::PruneColumn(thr, less) on this tile: keeps !(v < thr[column]) -> new tile."""
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, np.float64), (self.n,)))
+        t = Tile()
+        _check(lib().cbg_tile_prune_column(ctypes.byref(self.c), thr.ctypes.data, ctypes.byref(t.c)))
+        return t
 
     def split_cols(self, cut):
         """SpDCCols::Split (SpDCCols.cpp:905-930)"""
@@ -449,6 +481,29 @@ def phase_plan():
                               ctypes.byref(f), ctypes.byref(g))
     return dict(phases=a.value, automatic=bool(b.value), flops=c.value, nnz_est=d.value, c_budget_bytes=e.value,
                 oom_splits=f.value, plan_ms=g.value)
+
+
+MCL_STAT_NAMES = ("entries_in", "entries_out", "cols_recovered", "cols_selected", "cols_recovered_after", "pieces")
+MCL_KSELECT_CLASSES = ("wave", "lds_small", "lds_large", "stream")
+
+
+def mcl_kselect_bounds():
+    """upper column length of each k-select class but the last (cbg_mcl_kselect_bounds)"""
+    b = (ctypes.c_int64 * 3)()
+    n = lib().cbg_mcl_kselect_bounds(b, 3)
+    return [int(x) for x in b[:n]]
+
+
+def mcl_stats():
+    """The last pruning call's work (cbg_last_mcl_stats): entries in / out, columns
+    recovered / selected / recovered after selection, pieces, `kselect` = columns run
+    per k-select class, `ms` = device ms of the statistics, k-select and compaction."""
+    c, ms = (ctypes.c_int64 * 16)(), (ctypes.c_double * 3)()
+    lib().cbg_last_mcl_stats(c, 16, ms)
+    d = {k: int(c[i]) for i, k in enumerate(MCL_STAT_NAMES)}
+    d["kselect"] = {k: int(c[6 + i]) for i, k in enumerate(MCL_KSELECT_CLASSES)}
+    d["ms"] = dict(stats=ms[0], kselect=ms[1], compact=ms[2])
+    return d
 
 
 def merge_stats():
@@ -833,6 +888,22 @@ class SpParMat:
         self.tile = C
         return self
 
+    def PruneColumn(self, pvals):
+        """SpParMat::PruneColumn(pvals, less<>(), inPlace=false): keeps the entries with
+        !(v < pvals[column]); pvals: this rank's local columns (the slice of the
+        column-distributed vector that its grid column holds)."""
+        return SpParMat(self.tile.prune_column(pvals), self.grid, self.gm, self.gn)
+
+    def Kselect(self, cols, k):
+        """SpParMat::Kselect1 for the LOCAL column ids `cols` (the same list on every
+        rank of a grid column): their k-th largest value over the whole column, the
+        smallest where the column has fewer than k entries.  Collective over the grid."""
+        cols = np.ascontiguousarray(cols, np.int32)
+        kth = np.zeros(len(cols), np.float64)
+        _check(lib().cbg_grid_kselect(self.grid.h, ctypes.byref(self.tile.c), cols.ctypes.data, len(cols), int(k),
+                                      kth.ctypes.data))
+        return kth
+
     def copy(self):
         """deep copy (the reference's copy constructor)."""
         a, b = self.tile.split_cols(self.tile.n)
@@ -1038,7 +1109,8 @@ def Mult_AnXBn_Synch(A, B, sr=PlusTimesSRing, exec_mode=EXEC_PANEL):
 def MemEfficientSpGEMM(A, B, phases, sr=PlusTimesSRing, algo=DOUBLEBUFF, exec_mode=EXEC_PANEL, on_phase=None,
                        hardThreshold=0.0, selectNum=0, recoverNum=0, recoverPct=0.0, perProcessMemory=0):
     """ParFriends.h:449-730 with `phases` column pieces of B; the MCL pruning
-    arguments must stay at their no-pruning values (pruning is not on this path).
+    arguments must stay at their no-pruning values: the pruned product is
+    MemEfficientSpGEMM_MCL (this entry point keeps refusing them, as the suite pins).
 
     perProcessMemory > 0 (GB, ParFriends.h:482-535) or phases == PHASES_AUTO (this
     library's extension: the device's free memory) picks the phase count from
@@ -1050,6 +1122,33 @@ def MemEfficientSpGEMM(A, B, phases, sr=PlusTimesSRing, algo=DOUBLEBUFF, exec_mo
     each phase's device tile (valid during the call only) and None is returned."""
     if hardThreshold > 0 or selectNum > 0 or recoverNum > 0 or recoverPct > 0:
         raise CbgError(INVALIDPARAMS, "MemEfficientSpGEMM pruning (MCL) is not supported on this path")
+    return _memeff(A, B, phases, sr, algo, exec_mode, on_phase, perProcessMemory, None)
+
+
+def MCLPruneRecoverySelect(A, hardThreshold, selectNum, recoverNum, recoverPct, kselectVersion=1):
+    """ParFriends.h:186-353 on device, collective over A.grid; returns the pruned
+    matrix (A is left as it is).  kselectVersion is accepted and ignored (one exact
+    algorithm).  All parameters <= 0: a copy.  NaN values in A: unspecified."""
+    p = CMclParams(float(hardThreshold), int(selectNum), int(recoverNum), float(recoverPct))
+    out = Tile()
+    _check(lib().cbg_grid_mcl_prune(A.grid.h, ctypes.byref(A.tile.c), ctypes.byref(p), ctypes.byref(out.c)))
+    return SpParMat(out, A.grid, A.gm, A.gn)
+
+
+def MemEfficientSpGEMM_MCL(A, B, phases, hardThreshold, selectNum, recoverNum, recoverPct, kselectVersion=1,
+                           sr=PlusTimesSRing, algo=DOUBLEBUFF, exec_mode=EXEC_PANEL, on_phase=None,
+                           perProcessMemory=0):
+    """MemEfficientSpGEMM with its Markov-clustering pruning (ParFriends.h:449-730):
+    every column piece of C goes through MCLPruneRecoverySelect before it is
+    concatenated or handed to on_phase.  The other keywords are MemEfficientSpGEMM's,
+    which itself keeps refusing the pruning arguments.  All pruning parameters <= 0:
+    the unpruned product (the reference would drop negative values at threshold 0);
+    a negative selectNum / recoverNum or a NaN: INVALIDPARAMS."""
+    p = CMclParams(float(hardThreshold), int(selectNum), int(recoverNum), float(recoverPct))
+    return _memeff(A, B, phases, sr, algo, exec_mode, on_phase, perProcessMemory, p)
+
+
+def _memeff(A, B, phases, sr, algo, exec_mode, on_phase, perProcessMemory, mcl):
     errors = []  # (A is B is allowed: the reference copies B, ParFriends.h:547-549)
 
     def _cb(user, phase, off, ptile):
@@ -1066,9 +1165,12 @@ def MemEfficientSpGEMM(A, B, phases, sr=PlusTimesSRing, algo=DOUBLEBUFF, exec_mo
 
     fn = PHASE_FN(_cb) if on_phase is not None else PHASE_FN()
     C = Tile() if on_phase is None else None
-    rc = lib().cbg_summa_spgemm_memeff(A.grid.h, ctypes.byref(A.tile.c), ctypes.byref(B.tile.c), A.gn, B.gm, _sr(sr),
-                                       algo, exec_mode, phases, int(perProcessMemory), fn, None,
-                                       ctypes.byref(C.c) if C else None)
+    args = (A.grid.h, ctypes.byref(A.tile.c), ctypes.byref(B.tile.c), A.gn, B.gm, _sr(sr), algo, exec_mode, phases,
+            int(perProcessMemory), fn, None, ctypes.byref(C.c) if C else None)
+    if mcl is None:
+        rc = lib().cbg_summa_spgemm_memeff(*args)
+    else:
+        rc = lib().cbg_summa_spgemm_mcl(*args, ctypes.byref(mcl))
     if errors:
         raise errors[0]
     _check(rc)

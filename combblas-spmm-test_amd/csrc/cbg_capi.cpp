@@ -27,6 +27,11 @@ int agree(cbg_grid* g, int rc);
 std::string& step_error();
 int grid_block_extract(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, int dim, int64_t lo, int64_t hi,
                        cbg_tile& out);
+int grid_mcl_prune(cbg_grid* g, const cbg_tile& T, const cbg_mcl_params* p, cbg_tile& out);
+int grid_kselect(cbg_grid* g, const cbg_tile& T, const int32_t* cols, int64_t ncols, int64_t k, double* kth);
+int summa_spgemm_mcl(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr,
+                     int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C,
+                     const cbg_mcl_params& p);
 }  // namespace cbg
 
 namespace {
@@ -509,6 +514,128 @@ int cbg_summa_spgemm_memeff(cbg_grid* g, const cbg_tile* A, const cbg_tile* B, i
 int cbg_summa_spgemm_phased(cbg_grid* g, const cbg_tile* A, const cbg_tile* B, int64_t A_gncol, int64_t B_gnrow,
                             int sr, int algo, int exec, int phases, cbg_phase_fn fn, void* user, cbg_tile* C) {
   return cbg_summa_spgemm_memeff(g, A, B, A_gncol, B_gnrow, sr, algo, exec, phases, 0, fn, user, C);
+}
+
+// ---------------- Markov-clustering pruning ----------------
+// *active: some parameter asks for pruning (p == NULL or all <= 0: none)
+static int mcl_params(const cbg_mcl_params* p, bool* active) {
+  *active = false;
+  if (!p) return CBG_OK;
+  if (p->hard_threshold != p->hard_threshold || p->recover_pct != p->recover_pct)
+    return fail(CBG_ERR_INVALIDPARAMS, "MCL pruning: a parameter is NaN");
+  if (p->select_num < 0 || p->recover_num < 0)
+    return fail(CBG_ERR_INVALIDPARAMS, "MCL pruning: selectNum and recoverNum must not be negative");
+  *active = p->hard_threshold > 0 || p->select_num > 0 || p->recover_num > 0 || p->recover_pct > 0;
+  return CBG_OK;
+}
+
+// a host array of n per-column values on device
+static void upload_cols(cbg::DBuf<double>& d, const double* h, int64_t n, hipStream_t s) {
+  d.reset((size_t)std::max<int64_t>(n, 1));
+  if (n) CBG_HIP(hipMemcpyAsync(d.p, h, sizeof(double) * n, hipMemcpyHostToDevice, s));
+}
+
+int cbg_tile_col_stats(const cbg_tile* t, const double* thr, int strict, int64_t* cnt, double* sum) {
+  if (int rc = check_tile(t, true, "tile")) return rc;
+  if (t->n > 0 && (!thr || !cnt || !sum)) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_col_stats: an array is NULL");
+  if (strict != 0 && strict != 1) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_col_stats: strict is 0 or 1");
+  return guard([&] {
+    hipStream_t s = default_stream();
+    cbg::DBuf<double> dthr, dsum((size_t)std::max<int64_t>(t->n, 1));
+    cbg::DBuf<int64_t> dcnt((size_t)std::max<int64_t>(t->n, 1));
+    upload_cols(dthr, thr, t->n, s);
+    cbg::tile_col_stats_device(*t, dthr.p, strict, dcnt.p, dsum.p, s);
+    if (t->n) {
+      CBG_HIP(hipMemcpyAsync(cnt, dcnt.p, sizeof(int64_t) * t->n, hipMemcpyDeviceToHost, s));
+      CBG_HIP(hipMemcpyAsync(sum, dsum.p, sizeof(double) * t->n, hipMemcpyDeviceToHost, s));
+    }
+    CBG_HIP(hipStreamSynchronize(s));
+    return CBG_OK;
+  });
+}
+
+int cbg_tile_prune_column(const cbg_tile* t, const double* thr, cbg_tile* out) {
+  if (int rc = check_tile(t, true, "tile")) return rc;
+  if (!out || (t->n > 0 && !thr)) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_prune_column: thr or out is NULL");
+  return guard([&] {
+    hipStream_t s = default_stream();
+    cbg::DBuf<double> dthr;
+    upload_cols(dthr, thr, t->n, s);
+    cbg::tile_prune_column_device(*t, dthr.p, *out, s);
+    CBG_HIP(hipStreamSynchronize(s));
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_kselect(cbg_grid* g, const cbg_tile* local, const int32_t* cols, int64_t ncols, int64_t k, double* kth) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && (ncols < 0 || k < 1 || (ncols > 0 && (!cols || !kth))))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_kselect: k >= 1, ncols >= 0 and the arrays are needed");
+  const std::string why = g_err;
+  return guard([&]() -> int {
+    cbg::mcl_stats() = cbg::MclStats{};
+    if (arg) return fail(cbg::agree(g, arg), why);
+    CBG_HIP(hipDeviceSynchronize());
+    cbg::step_error().clear();
+    int rc = cbg::grid_kselect(g, *local, cols, ncols, k, kth);
+    if (rc == CBG_ERR_INVALIDPARAMS && cbg::step_error().empty())
+      return fail(rc, "cbg_grid_kselect: column ids outside the tile, listed twice, or lists that differ along the grid column");
+    if (rc) return fail(rc, cbg::step_error().empty() ? summa_msg(rc) : "this rank: " + cbg::step_error());
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_mcl_prune(cbg_grid* g, const cbg_tile* local, const cbg_mcl_params* p, cbg_tile* out) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && !out) arg = fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
+  bool active = false;
+  if (!arg) arg = mcl_params(p, &active);
+  const std::string why = g_err;
+  return guard([&]() -> int {
+    cbg::mcl_stats() = cbg::MclStats{};
+    if (arg) return fail(cbg::agree(g, arg), why);
+    CBG_HIP(hipDeviceSynchronize());
+    cbg::step_error().clear();
+    int rc = cbg::grid_mcl_prune(g, *local, active ? p : nullptr, *out);
+    if (rc) return fail(rc, cbg::step_error().empty() ? summa_msg(rc) : "this rank: " + cbg::step_error());
+    return CBG_OK;
+  });
+}
+
+int cbg_summa_spgemm_mcl(cbg_grid* g, const cbg_tile* A, const cbg_tile* B, int64_t A_gncol, int64_t B_gnrow, int sr,
+                         int algo, int exec, int phases, int64_t per_process_memory_gb, cbg_phase_fn fn, void* user,
+                         cbg_tile* C, const cbg_mcl_params* p) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = summa_args(A, B, sr, algo, exec);
+  if (!arg && !C && !fn) arg = fail(CBG_ERR_INVALIDPARAMS, "neither C nor a phase callback");
+  bool active = false;
+  if (!arg) arg = mcl_params(p, &active);
+  const std::string why = g_err;
+  return guard([&]() -> int {
+    cbg::thread_stats() = cbg::LocalStats{};
+    cbg::merge_stats() = cbg::MergeStats{};
+    cbg::mcl_stats() = cbg::MclStats{};
+    if (arg) return fail(cbg::agree(g, arg), why);
+    CBG_HIP(hipDeviceSynchronize());
+    cbg::step_error().clear();
+    int rc = active ? cbg::summa_spgemm_mcl(g, *A, *B, A_gncol, B_gnrow, sr, algo, exec, phases,
+                                            per_process_memory_gb, fn, user, C, *p)
+                    : cbg::summa_spgemm_phased(g, *A, *B, A_gncol, B_gnrow, sr, algo, exec, phases,
+                                               per_process_memory_gb, fn, user, C);
+    if (rc) return fail(rc, cbg::step_error().empty() ? summa_msg(rc) : "this rank: " + cbg::step_error());
+    return CBG_OK;
+  });
+}
+
+int cbg_mcl_kselect_bounds(int64_t* bounds, int n) { return cbg::mcl_kselect_bounds(bounds, n); }
+
+int cbg_last_mcl_stats(int64_t* counts, int n, double* ms) {
+  const cbg::MclStats& m = cbg::mcl_stats();
+  for (int i = 0; counts && i < n && i < CBG_MCL_N; ++i) counts[i] = m.counts[i];
+  for (int i = 0; ms && i < CBG_MCL_MS_N; ++i) ms[i] = m.ms[i];
+  return CBG_MCL_N;
 }
 
 int cbg_last_phase_plan(int* phases, int* automatic, int64_t* flops, int64_t* nnz_est, double* c_budget_bytes,

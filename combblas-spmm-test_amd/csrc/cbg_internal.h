@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -311,6 +312,30 @@ void restriction_tile(int scale, int order, uint64_t seed, int pr, int pc, int p
                       hipStream_t s);
 // values U[-1, 1) from a hash of (seed, global column, global row) (test inputs)
 void tile_random_values(cbg_tile& t, uint64_t seed, int64_t roff, int64_t coff, hipStream_t s);
+
+// Markov-clustering pruning (cbg_prune.hip)
+struct MclStats {
+  int64_t counts[CBG_MCL_N] = {};
+  double ms[CBG_MCL_MS_N] = {};
+};
+MclStats& mcl_stats();  // the calling thread's; reset by the C ABI's pruning entry points
+// the column communicator of a grid as the pruning sees it: agree_vals
+// allgathers (rc, vals[0..n)) over its P ranks into all[r * n + i] and returns
+// the largest rc; allgather_dev gathers device buffers of equal size
+struct ColComm {
+  int P = 1;
+  std::function<int(int rc, const int64_t* vals, int n, int64_t* all)> agree_vals;
+  std::function<void(const void* in, void* out, size_t bytes)> allgather_dev;
+};
+int mcl_kselect_bounds(int64_t* bounds, int n);
+void tile_col_stats_device(const cbg_tile& t, const double* thr, int strict, int64_t* cnt, double* sum,
+                           hipStream_t s);
+void tile_prune_column_device(const cbg_tile& t, const double* thr, cbg_tile& out, hipStream_t s);
+int grid_kselect_cols(const ColComm& cc, const cbg_tile& T, const int32_t* cols_host, int64_t ncols, int64_t k,
+                      double* kth_host, hipStream_t s);
+// pend: a failure of this rank from before the call (reported at the piece's first agreement)
+int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& P, cbg_tile& out, hipStream_t s,
+                    int pend = 0);
 
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);

@@ -1426,6 +1426,134 @@ int grid_block_extract(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, i
   return CBG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Markov-clustering pruning (MCLPruneRecoverySelect, ParFriends.h:186-353; the
+// kernels and the per-piece logic are in cbg_prune.hip).  All of its
+// collectives run along the grid column; the world only agrees on the result.
+// ---------------------------------------------------------------------------
+static ColComm col_comm(cbg_grid* g) {
+  ColComm cc;
+  cc.P = g->pr;
+  cc.agree_vals = [g](int rc, const int64_t* vals, int n, int64_t* all) {
+    const int P = g->pr;
+    if (P == 1) {
+      for (int i = 0; i < n; ++i) all[i] = vals[i];
+      return rc;
+    }
+    std::vector<int64_t> in((size_t)n + 1), out((size_t)P * (n + 1));
+    in[0] = rc;
+    for (int i = 0; i < n; ++i) in[i + 1] = vals[i];
+    allgather_i64(g, COMM_COL, in.data(), out.data(), n + 1);
+    int64_t w = 0;
+    for (int r = 0; r < P; ++r) {
+      w = std::max(w, out[(size_t)r * (n + 1)]);
+      for (int i = 0; i < n; ++i) all[(size_t)r * n + i] = out[(size_t)r * (n + 1) + 1 + i];
+    }
+    return (int)w;
+  };
+  cc.allgather_dev = [g](const void* in, void* out, size_t bytes) { allgather_device(g, COMM_COL, in, out, bytes); };
+  return cc;
+}
+
+int grid_mcl_prune(cbg_grid* g, const cbg_tile& T, const cbg_mcl_params* p, cbg_tile& out) {
+  check_usable(g);
+  hipStream_t cs = g->compute;
+  int rc = CBG_OK;
+  const int local = step([&] {
+    if (!p) {
+      tile_slice_cols(T, 0, T.n, out, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+    } else {
+      rc = mcl_prune_piece(col_comm(g), T, *p, out, cs);
+    }
+  });
+  return agree(g, std::max(local, rc));
+}
+
+int grid_kselect(cbg_grid* g, const cbg_tile& T, const int32_t* cols, int64_t ncols, int64_t k, double* kth) {
+  check_usable(g);
+  int rc = CBG_OK;
+  const int local = step([&] { rc = grid_kselect_cols(col_comm(g), T, cols, ncols, k, kth, g->compute); });
+  return agree(g, std::max(local, rc));
+}
+
+// The phased driver's consumer for the pruned product.  Pruning is per column,
+// so any column piece can be pruned on its own -- if the ranks of a grid column
+// prune the same columns at the same time.  Their B tiles have the same width,
+// so the phase cuts and the pipeline's cuts (functions of that width, the
+// world's narrowest tile and the environment; the adaptive decision is agreed
+// over the world) are the same; only the out-of-memory split of
+// multiply_to_fn is a rank's own decision.  So the ranks of a column first
+// allgather the width they hold and prune the narrowest (halves nest, every
+// rank reaches the end of the delivered piece at the same column), slicing
+// their piece where a peer holds a half.
+struct MclPhase {
+  cbg_grid* g;
+  cbg_mcl_params p;
+  cbg_phase_fn fn;
+  void* user;
+  ColComm cc;
+  std::vector<TileGuard> parts;
+  std::vector<int64_t> offs;
+  int rc = 0;     // a pruning failure, agreed along the grid column: no collective after it
+  int cb_rc = 0;  // the caller's fn failed
+};
+static int mcl_phase_fn(void* user, int phase, int64_t off, const cbg_tile* Cp) {
+  MclPhase& c = *static_cast<MclPhase*>(user);
+  if (c.rc) return c.rc;
+  hipStream_t cs = c.g->compute;
+  for (int64_t done = 0; done < Cp->n || (Cp->n == 0 && done == 0);) {
+    int64_t w = Cp->n - done;
+    if (c.cc.P > 1) {
+      std::vector<int64_t> all(c.cc.P);
+      if ((c.rc = c.cc.agree_vals(CBG_OK, &w, 1, all.data()))) return c.rc;
+      w = *std::min_element(all.begin(), all.end());
+    }
+    TileGuard slice, pruned;
+    int pend = CBG_OK;
+    const bool whole = done == 0 && w == Cp->n;
+    if (!whole) pend = step([&] { tile_slice_cols(*Cp, done, done + w, slice.t, cs); });
+    if (pend && c.cc.P == 1) return c.rc = pend;
+    int rc = CBG_OK;
+    const int local = step([&] { rc = mcl_prune_piece(c.cc, whole ? *Cp : slice.t, c.p, pruned.t, cs, pend); });
+    if ((c.rc = std::max(local, rc))) return c.rc;
+    if (c.fn) {
+      const int r = c.fn(c.user, phase, off + done, &pruned.t);
+      if (r && !c.cb_rc) c.cb_rc = r;
+    } else {
+      c.offs.push_back(off + done);
+      c.parts.push_back(std::move(pruned));
+    }
+    done += std::max<int64_t>(w, 1);
+  }
+  return CBG_OK;
+}
+
+int summa_spgemm_mcl(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr,
+                     int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C,
+                     const cbg_mcl_params& p) {
+  MclPhase c{g, p, fn, user, col_comm(g)};
+  int rc = summa_spgemm_phased(g, A, B, A_gncol, B_gnrow, sr, algo, exec, phases, mem_gb, mcl_phase_fn, &c, nullptr);
+  // the driver reports a consumer's failure as INVALIDPARAMS: the pruning's own code instead
+  if (rc == CBG_OK || rc == CBG_ERR_INVALIDPARAMS) {
+    const int mine = c.rc ? c.rc : c.cb_rc ? (int)CBG_ERR_INVALIDPARAMS : (int)CBG_OK;
+    const int a = agree(g, mine);
+    if (a) return a;
+  }
+  if (rc || fn) return rc;
+  rc = step([&] {
+    if (c.parts.size() == 1 && c.parts[0].t.n == B.n) {
+      *C = c.parts[0].release();
+    } else {
+      std::vector<cbg_tile> pv;
+      for (auto& t : c.parts) pv.push_back(t.t);
+      tile_concat_cols(pv, c.offs, A.m, B.n, *C, g->compute);
+      CBG_HIP(hipStreamSynchronize(g->compute));
+    }
+  });
+  return agree(g, rc);
+}
+
 }  // namespace cbg
 
 extern "C" int cbg_get_unique_id(void* id) {

@@ -14,7 +14,8 @@
 //   Mult_AnXBn_DoubleBuff      ParFriends.h:798   Mult_AnXBn_DoubleBuff
 //   Mult_AnXBn_Synch           ParFriends.h:1004  Mult_AnXBn_Synch
 //   PSpGEMM                    SpParMat.h:454     PSpGEMM
-//   MemEfficientSpGEMM         ParFriends.h:449   MemEfficientSpGEMM (phases; no MCL pruning)
+//   MemEfficientSpGEMM         ParFriends.h:449   MemEfficientSpGEMM (phases; MCL pruning when an argument is > 0)
+//   MCLPruneRecoverySelect     ParFriends.h:186   MCLPruneRecoverySelect, SpParMat::PruneColumn / Kselect
 //   SpParMat::Transpose        SpParMat.cpp:3528  Transpose (square grids, RCCL send/recv)
 //   SpParMat::DimApply         SpParMat.cpp:801   DimApply (dense vector given as its global values)
 //   SpParMat::ReadDistribute   SpParMat.cpp:4211  ReadDistribute (text / HKDT binary triples)
@@ -576,6 +577,29 @@ class SpParMat {
     spSeq->reset(c);
     return *this;
   }
+  // SpParMat::PruneColumn(pvals, less<NT>(), inPlace) (SpParMat.cpp): keeps the
+  // entries with !(v < pvals[column]); pvals: one value per LOCAL column (this
+  // rank's slice of the column-distributed vector).  Returns the pruned matrix,
+  // and with inPlace also replaces *this by it (the reference then returns an empty one).
+  SpParMat PruneColumn(const std::vector<double>& pvals, bool inPlace = false) {
+    if ((int64_t)pvals.size() != spSeq->tile()->n) cbg_abort_on(CBG_ERR_DIMMISMATCH, "PruneColumn: vector length");
+    cbg_tile t{};
+    cbg_abort_on(cbg_tile_prune_column(spSeq->tile(), pvals.data(), &t), "PruneColumn");
+    if (!inPlace) return SpParMat(new DER(t), commGrid, m_, n_);
+    spSeq->reset(t);
+    return SpParMat(commGrid);
+  }
+  // SpParMat::Kselect1 (SpParMat.cpp:1413-1739) for the LOCAL column ids `cols`
+  // (distinct; the same list on every rank of a grid column): the k-th largest
+  // value of each over the whole column, duplicates counted, the smallest where
+  // the column has fewer than k entries.  Collective over the grid.
+  std::vector<double> Kselect(const std::vector<int32_t>& cols, IT k) const {
+    std::vector<double> kth(cols.size());
+    cbg_abort_on(cbg_grid_kselect(commGrid->handle(), spSeq->tile(), cols.data(), (int64_t)cols.size(), (int64_t)k,
+                                  kth.data()),
+                 "Kselect");
+    return kth;
+  }
   // restriction operator (mfiles/genrestrict.m role): n x n/order
   static SpParMat restriction(std::shared_ptr<CommGrid> g, int scale, int order, uint64_t seed = 0x5EED) {
     cbg_tile t{};
@@ -686,8 +710,10 @@ SpParMat<IU, NUO, UDERO> Mult_AnXBn_Synch(SpParMat<IU, NU1, UDERA>& A, SpParMat<
   return detail::summa<SR, NUO, UDERO>(A, B, CBG_SYNCH, clearA, clearB, exec);
 }
 // ParFriends.h:449-451 signature.  Phases cut B's local tile by columns and C is
-// column-concatenated; the Markov-clustering pruning arguments must keep their
-// no-pruning values (hardThreshold, selectNum, recoverNum, recoverPct <= 0);
+// column-concatenated; when a Markov-clustering pruning argument (hardThreshold,
+// selectNum, recoverNum, recoverPct) is > 0 every column piece of C goes through
+// MCLPruneRecoverySelect first (cbg_summa_spgemm_mcl); all <= 0: no pruning (the
+// reference would drop negative values at a zero threshold);
 // perProcessMemory > 0 (GB) picks the phase count from memory like the
 // reference (ParFriends.h:482-535; see cbg_summa_spgemm_memeff), phases < 1 is
 // reset to 1 (:469-473); kselectVersion/computationKernel select CPU kernels of
@@ -699,16 +725,27 @@ SpParMat<IU, NUO, UDERO> MemEfficientSpGEMM(SpParMat<IU, NU1, UDERA>& A, SpParMa
                                              int kselectVersion, int computationKernel, int64_t perProcessMemory) {
   (void)kselectVersion;
   (void)computationKernel;
-  if (hardThreshold > 0 || selectNum > 0 || recoverNum > 0 || recoverPct > 0)
-    cbg_abort_on(CBG_ERR_INVALIDPARAMS, "MemEfficientSpGEMM: pruning is not supported");
   if (A.getncol() != B.getnrow()) cbg_abort_on(CBG_ERR_DIMMISMATCH, "Can not multiply, dimensions does not match");
   if (phases < 1) phases = 1;
   cbg_tile c{};
-  cbg_abort_on(cbg_summa_spgemm_memeff(A.commGrid->handle(), A.spSeq->tile(), B.spSeq->tile(), A.getncol(),
-                                       B.getnrow(), SR::code, CBG_DOUBLEBUFF, CBG_EXEC_PANEL, phases,
-                                       perProcessMemory > 0 ? perProcessMemory : 0, nullptr, nullptr, &c),
+  const cbg_mcl_params p = {(double)hardThreshold, (int64_t)selectNum, (int64_t)recoverNum, (double)recoverPct};
+  cbg_abort_on(cbg_summa_spgemm_mcl(A.commGrid->handle(), A.spSeq->tile(), B.spSeq->tile(), A.getncol(), B.getnrow(),
+                                    SR::code, CBG_DOUBLEBUFF, CBG_EXEC_PANEL, phases,
+                                    perProcessMemory > 0 ? perProcessMemory : 0, nullptr, nullptr, &c, &p),
                "MemEfficientSpGEMM");
   return SpParMat<IU, NUO, UDERO>(new UDERO(c), A.commGrid, A.getnrow(), B.getncol());
+}
+
+// ParFriends.h:186 signature: A is pruned in place (collective over its grid).
+// kselectVersion chooses between CPU algorithms of the reference and is unused.
+template <typename IT, typename NT, typename DER>
+void MCLPruneRecoverySelect(SpParMat<IT, NT, DER>& A, NT hardThreshold, IT selectNum, IT recoverNum, NT recoverPct,
+                            int kselectVersion) {
+  (void)kselectVersion;
+  const cbg_mcl_params p = {(double)hardThreshold, (int64_t)selectNum, (int64_t)recoverNum, (double)recoverPct};
+  cbg_tile t{};
+  cbg_abort_on(cbg_grid_mcl_prune(A.commGrid->handle(), A.spSeq->tile(), &p, &t), "MCLPruneRecoverySelect");
+  A.spSeq->reset(t);
 }
 
 // BlockSpGEMM (BlockSpGEMM.h:14-131): C = A*B block by block, A split into br

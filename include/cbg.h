@@ -263,7 +263,7 @@ int cbg_summa_spgemm(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* B_loc
                      int64_t B_gnrow, int semiring, int algo, int exec, cbg_tile* C_local);
 
 /* MemEfficientSpGEMM (ParFriends.h:449-730) without its Markov-clustering
- * pruning: this rank's B tile is cut into `phases` column pieces
+ * pruning (with it: cbg_summa_spgemm_mcl below): this rank's B tile is cut into `phases` column pieces
  * (SpDCCols::ColSplit, SpDCCols.cpp:936-970: cuts at (i+1)*(n/phases)), each
  * piece goes through the SUMMA above, and the phase results are
  *   fn == NULL: column-concatenated on device into C_local
@@ -304,6 +304,74 @@ int cbg_summa_spgemm_memeff(cbg_grid* g, const cbg_tile* A_local, const cbg_tile
  * host ms the planning took */
 int cbg_last_phase_plan(int* phases, int* automatic, int64_t* flops, int64_t* nnz_est, double* c_budget_bytes,
                         int* oom_splits, double* plan_ms);
+
+/* ---------------- Markov-clustering pruning (HipMCL) ---------------- */
+/* MCLPruneRecoverySelect (ParFriends.h:186-353) on device.  Every decision is per
+ * GLOBAL column j of the distributed matrix, over the row blocks of its grid column:
+ *   1. cnt0[j] = #{v > h}, sum0[j] = their sum, all[j] = nnz of the column; thr[j] = h;
+ *   2. recovery: columns with cnt0 < R, all > cnt0 and sum0 < q get thr = kth(j, R);
+ *   3. if S > 0: the other columns with cnt0 > S get thr = kth(j, S); if also R > 0,
+ *      those of them whose count and sum of the kept values (!(v < thr)) are < R and
+ *      < q get thr = kth(j, R);
+ *   4. v is kept iff !(v < thr[j]); emptied columns leave jc.
+ * kth(j, k) is the k-th largest value of the unpruned column, duplicates counted
+ * (SpParMat::Kselect1, SpParMat.cpp:1413-1739), its smallest value when it has fewer
+ * than k entries: ties with the k-th value are all kept.  -0.0 and +0.0 compare equal
+ * (a k-th value of zero is returned as +0.0); the result for a column that holds a
+ * NaN is unspecified.  kselectVersion has no counterpart (one exact algorithm). */
+typedef struct cbg_mcl_params {
+  double hard_threshold;
+  int64_t select_num, recover_num;
+  double recover_pct;
+} cbg_mcl_params;
+/* Column statistics of a device tile: cnt[j] / sum[j] = number / sum of the values of
+ * local column j kept under thr[j] (strict: 1 keeps v > thr, 0 keeps !(v < thr)); 0 for
+ * empty columns.  thr, cnt, sum are HOST arrays of t->n entries.  The order of a
+ * column's sum depends on its length alone (bit-reproducible). */
+int cbg_tile_col_stats(const cbg_tile* t, const double* thr, int strict, int64_t* cnt, double* sum);
+/* SpParMat::PruneColumn(pvals, less<>) (SpParMat.cpp) on one tile: out keeps the
+ * entries with !(v < thr[column]), values copied; thr: HOST array of t->n entries */
+int cbg_tile_prune_column(const cbg_tile* t, const double* thr, cbg_tile* out);
+/* SpParMat::Kselect1, collective along the grid column (every rank of the grid calls
+ * it; the ranks of a grid column list the same columns): kth[i] = the k-th largest
+ * value of local column cols[i] over the grid column's row blocks (the smallest when
+ * the column has fewer than k entries, 0.0 when it is empty).  cols: distinct local
+ * column ids (HOST), kth: HOST out.  k >= 1. */
+int cbg_grid_kselect(cbg_grid* g, const cbg_tile* local, const int32_t* cols, int64_t ncols, int64_t k, double* kth);
+/* MCLPruneRecoverySelect of the distributed matrix whose tile is `local`; out = this
+ * rank's pruned tile.  select_num < 0, recover_num < 0 or a NaN parameter:
+ * CBG_ERR_INVALIDPARAMS.  p == NULL or every parameter <= 0: out is a copy. */
+int cbg_grid_mcl_prune(cbg_grid* g, const cbg_tile* local, const cbg_mcl_params* p, cbg_tile* out);
+/* cbg_summa_spgemm_memeff with every delivered column piece of C pruned
+ * (MCLPruneRecoverySelect, ParFriends.h:698) before it is concatenated or handed to
+ * fn (same phase and col_offset).  p == NULL or every parameter <= 0: no pruning,
+ * the result of cbg_summa_spgemm_memeff (the reference would drop negative values
+ * at a zero threshold). */
+int cbg_summa_spgemm_mcl(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* B_local, int64_t A_gncol,
+                         int64_t B_gnrow, int semiring, int algo, int exec, int phases,
+                         int64_t per_process_memory_gb, cbg_phase_fn fn, void* user, cbg_tile* C_local,
+                         const cbg_mcl_params* p);
+/* upper column length of each k-select kernel class but the last (a wave's registers,
+ * a block's LDS in two sizes; longer columns are streamed): bounds[i] for
+ * i < min(n, 3); returns 3 */
+int cbg_mcl_kselect_bounds(int64_t* bounds, int n);
+/* the last pruning call's work, summed over its pieces: entries in / out, columns
+ * recovered, selected, recovered after selection, pieces pruned, columns run by each
+ * k-select class (for grid columns of several ranks: of the union pass).
+ * counts[i] for i < min(n, CBG_MCL_N); ms (may be NULL): CBG_MCL_MS_N device times
+ * (statistics, k-select, compaction).  Returns CBG_MCL_N. */
+enum {
+  CBG_MCL_ENTRIES_IN = 0,
+  CBG_MCL_ENTRIES_OUT = 1,
+  CBG_MCL_COLS_RECOVERED = 2,
+  CBG_MCL_COLS_SELECTED = 3,
+  CBG_MCL_COLS_RECOVERED_AFTER = 4,
+  CBG_MCL_PIECES = 5,
+  CBG_MCL_KSELECT_CLASS0 = 6, /* + c: wave, LDS small, LDS large, streamed */
+  CBG_MCL_N = 10
+};
+enum { CBG_MCL_MS_STATS = 0, CBG_MCL_MS_KSELECT = 1, CBG_MCL_MS_COMPACT = 2, CBG_MCL_MS_N = 3 };
+int cbg_last_mcl_stats(int64_t* counts, int n, double* ms);
 
 /* SpParMat::Transpose (SpParMat.cpp:3528-3590), collective over a square grid:
  * out = this rank's tile of the transposed matrix (the transpose of the
