@@ -85,7 +85,25 @@ EXPORTS = [
     "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_store_probe",
     "cbg_tile_col_stats", "cbg_tile_prune_column", "cbg_grid_kselect", "cbg_grid_mcl_prune", "cbg_summa_spgemm_mcl",
     "cbg_mcl_kselect_bounds", "cbg_last_mcl_stats",
+    "cbg_grid_reduce_cols", "cbg_mcl_moment_bounds", "cbg_tile_apply", "cbg_grid_make_col_stochastic", "cbg_grid_chaos",
+    "cbg_grid_inflate", "cbg_last_inflate_stats", "cbg_grid_remove_loops", "cbg_grid_add_loops", "cbg_grid_adjust_loops",
+    "cbg_grid_connected_components", "cbg_grid_hipmcl", "cbg_last_hipmcl_stats",
 ]
+RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT = 0, 1, 2, 3  # cbg_grid_reduce_cols
+_REDS = {"sum": RED_SUM, "plus": RED_SUM, "max": RED_MAX, "maximum": RED_MAX, "sumsq": RED_SUMSQ, "count": RED_COUNT}
+APPLY_POW = 0
+
+
+class CHipMclParams(ctypes.Structure):
+    """cbg_hipmcl_params (include/cbg.h)"""
+    _fields_ = [("inflation", ctypes.c_double), ("prune", CMclParams), ("phases", ctypes.c_int32),
+                ("algo", ctypes.c_int32), ("exec", ctypes.c_int32), ("preprune", ctypes.c_int32),
+                ("per_process_memory_gb", ctypes.c_int64), ("eps", ctypes.c_double), ("max_iterations", ctypes.c_int64)]
+
+
+# void (*cbg_hipmcl_iter_fn)(void* user, int64 iter, double chaos, int64 nnz, double ms_expand, ms_prune, ms_inflate)
+HIPMCL_ITER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double)
 Column, Row = 0, 1  # DimApply dimensions (SpDefs.h Dim)
 OP_MULTIPLIES, OP_PLUS, OP_MIN, OP_MAX = 0, 1, 2, 3
 _OPS = {"multiplies": OP_MULTIPLIES, "plus": OP_PLUS, "min": OP_MIN, "max": OP_MAX}
@@ -168,6 +186,21 @@ def lib():
                                   ctypes.POINTER(CMclParams)], i32),
         "cbg_mcl_kselect_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_mcl_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_grid_reduce_cols": ([vp, T, i32, ctypes.c_double, vp], i32),
+        "cbg_mcl_moment_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_tile_apply": ([T, i32, ctypes.c_double], i32),
+        "cbg_grid_make_col_stochastic": ([vp, T], i32),
+        "cbg_grid_chaos": ([vp, T, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_grid_inflate": ([vp, T, ctypes.c_double, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_last_inflate_stats": ([ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)], i32),
+        "cbg_grid_remove_loops": ([vp, T, i64, i64, T, ctypes.POINTER(i64)], i32),
+        "cbg_grid_add_loops": ([vp, T, i64, i64, vp, i32, T], i32),
+        "cbg_grid_adjust_loops": ([vp, T, i64, i64, T], i32),
+        "cbg_grid_connected_components": ([vp, T, i64, vp, ctypes.POINTER(i64)], i32),
+        "cbg_grid_hipmcl": ([vp, T, i64, ctypes.POINTER(CHipMclParams), HIPMCL_ITER_FN, vp, T, vp, ctypes.POINTER(i64),
+                             ctypes.POINTER(i64)], i32),
+        "cbg_last_hipmcl_stats": ([ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
+                                  + [ctypes.POINTER(ctypes.c_double)] * 3, i32),
     }
     experiment = "CBG_LIB" in os.environ  # an older build under A/B may lack the newest entry points
     for name, (args, res) in sig.items():
@@ -904,6 +937,79 @@ class SpParMat:
                                       kth.ctypes.data))
         return kth
 
+    # ---- the HipMCL iteration (Applications/MCL.cpp) ----
+    def _local_cols(self, vec):
+        """this rank's slice of a dense global column vector (or one value for all columns)"""
+        v = np.asarray(vec, np.float64)
+        if v.ndim == 0:
+            return np.full(self.tile.n, float(v))
+        lo, hi = block_range(self.gn, self.grid.grid_cols, self.grid.pcol)
+        return np.ascontiguousarray(v[lo:hi])
+
+    def Reduce(self, dim, op, identity=0.0):
+        """SpParMat::Reduce(Column, op, id[, unop]): op "sum", "max", "sumsq" (plus over
+        exponentiate(., 2)) or "count" (plus over 1.0); returns the values of this rank's
+        local columns over their whole grid column (`identity` for empty ones)."""
+        if dim != Column:
+            raise CbgError(NOTSUPPORTED, "Reduce: columns only")
+        what = _REDS.get(op, op) if isinstance(op, str) else op
+        if what not in (RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT):
+            raise CbgError(INVALIDPARAMS, f"Reduce: unknown op {op!r} (sum, max, sumsq, count or a RED_* code)")
+        out = np.zeros(max(self.tile.n, 1), np.float64)
+        _check(lib().cbg_grid_reduce_cols(self.grid.h, ctypes.byref(self.tile.c), int(what), float(identity),
+                                          out.ctypes.data))
+        return out[:self.tile.n]
+
+    def Apply(self, op, arg):
+        """SpParMat::Apply(bind2nd(exponentiate(), arg)) (op "pow"), in place."""
+        if op != "pow" and not (isinstance(op, int) and op == APPLY_POW):
+            raise CbgError(INVALIDPARAMS, f"Apply: unknown op {op!r} (\"pow\" or APPLY_POW)")
+        _check(lib().cbg_tile_apply(ctypes.byref(self.tile.c), APPLY_POW, float(arg)))
+
+    def MakeColStochastic(self):
+        """MCL.cpp:390-395, in place."""
+        _check(lib().cbg_grid_make_col_stochastic(self.grid.h, ctypes.byref(self.tile.c)))
+
+    def Chaos(self):
+        """MCL.cpp:408-421"""
+        c = ctypes.c_double()
+        _check(lib().cbg_grid_chaos(self.grid.h, ctypes.byref(self.tile.c), ctypes.byref(c)))
+        return c.value
+
+    def Inflate(self, power):
+        """MakeColStochastic, Chaos, Inflate(power), MakeColStochastic (MCL.cpp:591-611) fused
+        in three passes, in place; returns the chaos (of the matrix before the inflation)."""
+        c = ctypes.c_double()
+        _check(lib().cbg_grid_inflate(self.grid.h, ctypes.byref(self.tile.c), float(power), ctypes.byref(c)))
+        return c.value
+
+    def _swap(self, t):
+        self.tile.free()
+        self.tile = t
+
+    def RemoveLoops(self):
+        """SpParMat::RemoveLoops (SpParMat.cpp:3257-3272), in place; returns the loops removed."""
+        t, rem = Tile(), ctypes.c_int64()
+        _check(lib().cbg_grid_remove_loops(self.grid.h, ctypes.byref(self.tile.c), self.gm, self.gn, ctypes.byref(t.c),
+                                           ctypes.byref(rem)))
+        self._swap(t)
+        return rem.value
+
+    def AddLoops(self, loopvals, replaceExisting=False):
+        """SpParMat::AddLoops (SpParMat.cpp:3277-3335), in place: loopvals one value or a dense
+        global vector of ncol values."""
+        v = self._local_cols(loopvals)
+        t = Tile()
+        _check(lib().cbg_grid_add_loops(self.grid.h, ctypes.byref(self.tile.c), self.gm, self.gn, v.ctypes.data,
+                                        int(bool(replaceExisting)), ctypes.byref(t.c)))
+        self._swap(t)
+
+    def AdjustLoops(self):
+        """MCL.cpp:464-474, in place (an empty column's loop is numeric_limits<double>::min())."""
+        t = Tile()
+        _check(lib().cbg_grid_adjust_loops(self.grid.h, ctypes.byref(self.tile.c), self.gm, self.gn, ctypes.byref(t.c)))
+        self._swap(t)
+
     def copy(self):
         """deep copy (the reference's copy constructor)."""
         a, b = self.tile.split_cols(self.tile.n)
@@ -1146,6 +1252,83 @@ def MemEfficientSpGEMM_MCL(A, B, phases, hardThreshold, selectNum, recoverNum, r
     a negative selectNum / recoverNum or a NaN: INVALIDPARAMS."""
     p = CMclParams(float(hardThreshold), int(selectNum), int(recoverNum), float(recoverPct))
     return _memeff(A, B, phases, sr, algo, exec_mode, on_phase, perProcessMemory, p)
+
+
+def mcl_moment_bounds():
+    """upper column length of each column-moment kernel class but the last (cbg_mcl_moment_bounds)"""
+    b = (ctypes.c_int64 * 2)()
+    n = lib().cbg_mcl_moment_bounds(b, 2)
+    return [int(x) for x in b[:n]]
+
+
+def inflate_stats():
+    """device ms of the last Inflate's three passes on this rank and the entries they ran over"""
+    ms, nnz = (ctypes.c_double * 3)(), ctypes.c_int64()
+    lib().cbg_last_inflate_stats(ms, ctypes.byref(nnz))
+    return dict(ms=[float(x) for x in ms], nnz=int(nnz.value))
+
+
+def hipmcl_stats():
+    """the last HipMCL call (cbg_last_hipmcl_stats)"""
+    it, nnz, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+    ms = [ctypes.c_double() for _ in range(3)]
+    lib().cbg_last_hipmcl_stats(ctypes.byref(it), ctypes.byref(c), ctypes.byref(nnz), *[ctypes.byref(x) for x in ms])
+    return dict(iterations=int(it.value), chaos=c.value, final_nnz=int(nnz.value), ms_expand=ms[0].value,
+                ms_prune=ms[1].value, ms_inflate=ms[2].value)
+
+
+def Interpret(A):
+    """Interpret (MCL.cpp:373-386): the connected components of A + A^T (not built) ->
+    labels[v] = the rank of v's component, components ordered by their smallest vertex."""
+    labels = np.zeros(max(A.gn, 1), np.int64)
+    nc = ctypes.c_int64()
+    _check(lib().cbg_grid_connected_components(A.grid.h, ctypes.byref(A.tile.c), A.gn, labels.ctypes.data,
+                                               ctypes.byref(nc)))
+    return labels[:A.gn]
+
+
+def HipMCL(A, inflation=2.0, prunelimit=1e-4, select=1100, recover_num=1400, recover_pct=0.9, phases=1,
+           perProcessMem=0, preprune=None, max_iterations=0, on_iteration=None, eps=0.0, algo=DOUBLEBUFF,
+           exec_mode=EXEC_PANEL, keep_final=False):
+    """HipMCL() (MCL.cpp:515-647) on device: returns (labels, iterations); A is left
+    unchanged.  preprune None: the reference's rule (average degree > max(S, R)).
+    on_iteration(iter, chaos, nnz, ms_expand, ms_prune, ms_inflate) once per iteration.
+    max_iterations > 0 stops there (hipmcl_stats()["chaos"] tells whether it converged).
+    keep_final: also returns the converged matrix, (labels, iterations, SpParMat)."""
+    p = CHipMclParams(float(inflation), CMclParams(float(prunelimit), int(select), int(recover_num), float(recover_pct)),
+                      int(phases), algo, exec_mode, -1 if preprune is None else int(bool(preprune)), int(perProcessMem),
+                      float(eps), int(max_iterations))
+    errors = []
+
+    def _cb(user, it, chaos, nnz, ms_e, ms_p, ms_i):
+        try:
+            on_iteration(int(it), chaos, int(nnz), ms_e, ms_p, ms_i)
+        except Exception as e:  # noqa: BLE001 -- reported after the collective finishes
+            errors.append(e)
+
+    cb = HIPMCL_ITER_FN(_cb) if on_iteration else HIPMCL_ITER_FN()
+    labels = np.zeros(max(A.gn, 1), np.int64)
+    nc, its = ctypes.c_int64(), ctypes.c_int64()
+    final = Tile()
+    _check(lib().cbg_grid_hipmcl(A.grid.h, ctypes.byref(A.tile.c), A.gn, ctypes.byref(p), cb, None,
+                                 ctypes.byref(final.c) if keep_final else None, labels.ctypes.data, ctypes.byref(nc),
+                                 ctypes.byref(its)))
+    if errors:
+        raise errors[0]
+    if keep_final:
+        return labels[:A.gn], int(its.value), SpParMat(final, A.grid, A.gn, A.gn)
+    return labels[:A.gn], int(its.value)
+
+
+def write_clusters(path, labels):
+    """one cluster per line, its members (vertex ids) separated by a space, as
+    WriteMCLClusters.h:28-42 describes; clusters in label order, members ascending"""
+    labels = np.asarray(labels, np.int64)
+    order = np.argsort(labels, kind="stable")
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    with open(path, "w") as f:
+        for grp in np.split(order, cuts) if len(order) else []:
+            f.write(" ".join(str(int(v)) for v in grp) + "\n")
 
 
 def _memeff(A, B, phases, sr, algo, exec_mode, on_phase, perProcessMemory, mcl):

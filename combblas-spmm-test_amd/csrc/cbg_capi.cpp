@@ -1,6 +1,7 @@
 // cbg_capi.cpp -- extern "C" boundary of libcbg (declared in include/cbg.h).
 // Every entry point catches exceptions and returns the reference's abort code
 // (SpDefs.h:69-76) or a >= 3100 runtime code; cbg_last_error() has the text.
+#include <cfloat>
 #include <cstring>
 
 #include "cbg_internal.h"
@@ -32,6 +33,17 @@ int grid_kselect(cbg_grid* g, const cbg_tile& T, const int32_t* cols, int64_t nc
 int summa_spgemm_mcl(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr,
                      int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C,
                      const cbg_mcl_params& p);
+int grid_reduce_cols(cbg_grid* g, const cbg_tile& T, int what, double identity, double* out);
+int grid_make_col_stochastic(cbg_grid* g, cbg_tile& T);
+int grid_chaos(cbg_grid* g, const cbg_tile& T, double* chaos);
+int grid_inflate(cbg_grid* g, cbg_tile& T, double power, double* chaos);
+int grid_remove_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out, int64_t* removed);
+int grid_add_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const double* loopvals, int replace,
+                   cbg_tile& out);
+int grid_adjust_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out);
+int grid_connected_components(cbg_grid* g, const cbg_tile& T, int64_t gn, int64_t* labels, int64_t* ncomp);
+int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P, cbg_hipmcl_iter_fn fn,
+                void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters, int64_t* iterations);
 }  // namespace cbg
 
 namespace {
@@ -636,6 +648,148 @@ int cbg_last_mcl_stats(int64_t* counts, int n, double* ms) {
   for (int i = 0; counts && i < n && i < CBG_MCL_N; ++i) counts[i] = m.counts[i];
   for (int i = 0; ms && i < CBG_MCL_MS_N; ++i) ms[i] = m.ms[i];
   return CBG_MCL_N;
+}
+
+// ---------------- HipMCL iteration ----------------
+// a collective entry point's frame: the argument error (if any) is agreed before any device work
+extern "C++" template <class F>
+static int grid_call(cbg_grid* g, int arg, F&& f) {
+  const std::string why = g_err;
+  return guard([&]() -> int {
+    if (arg) return fail(cbg::agree(g, arg), why);
+    CBG_HIP(hipDeviceSynchronize());
+    cbg::step_error().clear();
+    const int rc = f();
+    if (rc == CBG_ERR_DIMMISMATCH && cbg::step_error().empty())
+      return fail(rc, "the matrix is not square, or the tile is not this rank's block of it");
+    if (rc == CBG_ERR_NOTSUPPORTED && cbg::step_error().empty())
+      return fail(rc, "connected components: no fixed point within gn rounds");
+    if (rc) return fail(rc, cbg::step_error().empty() ? summa_msg(rc) : "this rank: " + cbg::step_error());
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_reduce_cols(cbg_grid* g, const cbg_tile* local, int what, double identity, double* out) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && (what < CBG_RED_SUM || what > CBG_RED_COUNT || identity != identity || (local->n > 0 && !out)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_reduce_cols: what is CBG_RED_*, identity a number, out is needed");
+  return grid_call(g, arg, [&] { return cbg::grid_reduce_cols(g, *local, what, identity, out); });
+}
+
+int cbg_mcl_moment_bounds(int64_t* bounds, int n) { return cbg::mcl_moment_bounds(bounds, n); }
+
+int cbg_tile_apply(cbg_tile* t, int op, double arg) {
+  if (int rc = check_tile(t, true, "tile")) return rc;
+  if (op != CBG_APPLY_POW || arg != arg) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_apply: op is CBG_APPLY_POW, arg a number");
+  return guard([&] {
+    hipStream_t s = default_stream();
+    cbg::tile_apply_pow(*t, arg, s);
+    CBG_HIP(hipStreamSynchronize(s));
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_make_col_stochastic(cbg_grid* g, cbg_tile* local) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  return grid_call(g, check_tile(local, true, "tile"), [&] { return cbg::grid_make_col_stochastic(g, *local); });
+}
+
+int cbg_grid_chaos(cbg_grid* g, const cbg_tile* local, double* chaos) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && !chaos) arg = fail(CBG_ERR_INVALIDPARAMS, "chaos is NULL");
+  return grid_call(g, arg, [&] { return cbg::grid_chaos(g, *local, chaos); });
+}
+
+static int inflation_arg(double power) {
+  if (!(power > 0) || power > DBL_MAX) return fail(CBG_ERR_INVALIDPARAMS, "the inflation must be a positive finite number");
+  return CBG_OK;
+}
+
+int cbg_grid_inflate(cbg_grid* g, cbg_tile* local, double power, double* chaos) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && !chaos) arg = fail(CBG_ERR_INVALIDPARAMS, "chaos is NULL");
+  if (!arg) arg = inflation_arg(power);
+  return grid_call(g, arg, [&] { return cbg::grid_inflate(g, *local, power, chaos); });
+}
+
+int cbg_last_inflate_stats(double* ms3, int64_t* nnz) {
+  const cbg::HipMclStats& h = cbg::hipmcl_stats();
+  for (int i = 0; ms3 && i < 3; ++i) ms3[i] = h.inflate_ms[i];
+  if (nnz) *nnz = h.inflate_nnz;
+  return CBG_OK;
+}
+
+// gm != gn is refused here, before any device work (and again, agreed, with the tile's shape)
+static int loops_args(const cbg_tile* local, int64_t gm, int64_t gn, const void* out) {
+  if (int rc = check_tile(local, true, "tile")) return rc;
+  if (!out) return fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
+  if (gm != gn) return fail(CBG_ERR_DIMMISMATCH, "loops need a square matrix");
+  return CBG_OK;
+}
+
+int cbg_grid_remove_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, cbg_tile* out, int64_t* removed) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  return grid_call(g, loops_args(local, gm, gn, out),
+                   [&] { return cbg::grid_remove_loops(g, *local, gm, gn, *out, removed); });
+}
+
+int cbg_grid_add_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, const double* loopvals,
+                       int replace_existing, cbg_tile* out) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = loops_args(local, gm, gn, out);
+  if (!arg && local->n > 0 && !loopvals) arg = fail(CBG_ERR_INVALIDPARAMS, "loopvals is NULL");
+  return grid_call(g, arg, [&] { return cbg::grid_add_loops(g, *local, gm, gn, loopvals, replace_existing != 0, *out); });
+}
+
+int cbg_grid_adjust_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, cbg_tile* out) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  return grid_call(g, loops_args(local, gm, gn, out), [&] { return cbg::grid_adjust_loops(g, *local, gm, gn, *out); });
+}
+
+int cbg_grid_connected_components(cbg_grid* g, const cbg_tile* local, int64_t gn, int64_t* labels, int64_t* ncomponents) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && gn < 0) arg = fail(CBG_ERR_INVALIDPARAMS, "gn is negative");
+  return grid_call(g, arg, [&] { return cbg::grid_connected_components(g, *local, gn, labels, ncomponents); });
+}
+
+int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
+                    cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters,
+                    int64_t* iterations) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(A_local, true, "A");
+  if (!arg && !params) arg = fail(CBG_ERR_INVALIDPARAMS, "params is NULL");
+  if (!arg && gn < 0) arg = fail(CBG_ERR_INVALIDPARAMS, "gn is negative");
+  if (!arg) arg = inflation_arg(params->inflation);
+  bool active = false;
+  if (!arg) arg = mcl_params(&params->prune, &active);
+  if (!arg && params->max_iterations < 0) arg = fail(CBG_ERR_INVALIDPARAMS, "max_iterations is negative");
+  if (!arg && (params->eps != params->eps || params->preprune < -1 || params->preprune > 1 ||
+               (params->algo != CBG_DOUBLEBUFF && params->algo != CBG_SYNCH) ||
+               (params->exec != CBG_EXEC_PANEL && params->exec != CBG_EXEC_STAGED)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_hipmcl: eps is NaN, or preprune, algo or exec is out of range");
+  if (!arg && A_local->nnz + A_local->n >= INT32_MAX) arg = fail(CBG_ERR_NOTSUPPORTED, "A tiles need nnz < 2^31");
+  return grid_call(g, arg, [&] {
+    cbg::thread_stats() = cbg::LocalStats{};
+    cbg::merge_stats() = cbg::MergeStats{};
+    cbg::mcl_stats() = cbg::MclStats{};
+    return cbg::grid_hipmcl(g, *A_local, gn, *params, fn, user, final_local, labels, nclusters, iterations);
+  });
+}
+
+int cbg_last_hipmcl_stats(int64_t* iterations, double* chaos, int64_t* final_nnz, double* ms_expand, double* ms_prune,
+                          double* ms_inflate) {
+  const cbg::HipMclStats& h = cbg::hipmcl_stats();
+  if (iterations) *iterations = h.iterations;
+  if (chaos) *chaos = h.chaos;
+  if (final_nnz) *final_nnz = h.final_nnz;
+  if (ms_expand) *ms_expand = h.ms_expand;
+  if (ms_prune) *ms_prune = h.ms_prune;
+  if (ms_inflate) *ms_inflate = h.ms_inflate;
+  return CBG_OK;
 }
 
 int cbg_last_phase_plan(int* phases, int* automatic, int64_t* flops, int64_t* nnz_est, double* c_budget_bytes,

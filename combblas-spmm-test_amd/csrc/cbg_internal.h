@@ -337,6 +337,32 @@ int grid_kselect_cols(const ColComm& cc, const cbg_tile& T, const int32_t* cols_
 int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& P, cbg_tile& out, hipStream_t s,
                     int pend = 0);
 
+// the Markov-clustering iteration (cbg_mcl.hip); the *_device entry points are
+// collective along the grid column `cc` and end with an agreement on their code
+int mcl_moment_bounds(int64_t* bounds, int n);
+void tile_apply_pow(cbg_tile& t, double power, hipStream_t s);
+int grid_reduce_cols_device(const ColComm& cc, const cbg_tile& T, int what, double identity, double* out_host,
+                            hipStream_t s);
+int grid_make_col_stochastic_device(const ColComm& cc, cbg_tile& T, hipStream_t s);
+int grid_chaos_device(const ColComm& cc, const cbg_tile& T, double* chaos, hipStream_t s);  // the grid column's
+int grid_inflate_device(const ColComm& cc, cbg_tile& T, double power, double* chaos, hipStream_t s, double* ms3);
+// mode 0 removes the stored diagonal entries, 1 adds loopval[j] (device, n values) where
+// none is stored (replace: also over the stored ones); diag_off = the tile's column
+// offset minus its row offset; fix_min: AdjustLoops' Apply; found: diagonal entries stored
+void tile_edit_loops_device(const cbg_tile& T, int64_t diag_off, int mode, int replace, int fix_min,
+                            const double* loopval, cbg_tile& out, int64_t* found, hipStream_t s);
+void cc_init_device(uint64_t* L, int64_t gn, hipStream_t s);
+void cc_round_device(const cbg_tile& T, int64_t roff, int64_t coff, uint64_t* L, int64_t gn, uint64_t* changed,
+                     hipStream_t s);
+void cc_min_device(uint64_t* L, const uint64_t* all, int P, int64_t gn, uint64_t* changed, hipStream_t s);
+struct HipMclStats {
+  int64_t iterations = 0, final_nnz = 0;
+  double chaos = 0, ms_expand = 0, ms_prune = 0, ms_inflate = 0;
+  double inflate_ms[3] = {};  // the last cbg_grid_inflate's passes
+  int64_t inflate_nnz = 0;
+};
+HipMclStats& hipmcl_stats();
+
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);
 void store_probe(int64_t bytes, int width);

@@ -44,6 +44,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <thread>
 
@@ -421,7 +422,13 @@ static void bcast_tile(cbg_grid* g, int which, int root, const int64_t ess[4], c
     if (comm_size(g, which) == 1) return;
     CBG_HIP(hipStreamSynchronize(g->comm));
     auto hb = [&](void* dptr, size_t bytes) {
-      if (bytes == 0) return;
+      if (bytes == 0) {
+        // the host transport's collectives are synchronous over the WORLD: an empty tile in
+        // one grid row (column) must not skip an exchange that the other rows (columns) make
+        char none = 0;
+        host_check(g, g->hc.bcast(g->hc.user, which, &none, 1, root), "bcast");
+        return;
+      }
       std::vector<char> h(bytes);
       if (mine) CBG_HIP(hipMemcpy(h.data(), dptr, bytes, hipMemcpyDeviceToHost));
       host_check(g, g->hc.bcast(g->hc.user, which, h.data(), bytes, root), "bcast");
@@ -1552,6 +1559,231 @@ int summa_spgemm_mcl(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t 
     }
   });
   return agree(g, rc);
+}
+
+// ---------------------------------------------------------------------------
+// The HipMCL iteration (Applications/MCL.cpp:515-647; kernels and the
+// grid-column logic in cbg_mcl.hip).  Column reductions are collective along
+// the grid column; the world agrees on every step's code.
+// ---------------------------------------------------------------------------
+int grid_reduce_cols(cbg_grid* g, const cbg_tile& T, int what, double identity, double* out) {
+  check_usable(g);
+  int rc = CBG_OK;
+  const int local = step([&] { rc = grid_reduce_cols_device(col_comm(g), T, what, identity, out, g->compute); });
+  return agree(g, std::max(local, rc));
+}
+
+int grid_make_col_stochastic(cbg_grid* g, cbg_tile& T) {
+  check_usable(g);
+  int rc = CBG_OK;
+  const int local = step([&] { rc = grid_make_col_stochastic_device(col_comm(g), T, g->compute); });
+  return agree(g, std::max(local, rc));
+}
+
+// the grid column's chaos -> the world's
+static int world_chaos(cbg_grid* g, int rc, double* chaos) {
+  if ((rc = agree(g, rc))) return rc;
+  return agree(g, step([&] { allreduce_f64(g, chaos, true); }));
+}
+
+int grid_chaos(cbg_grid* g, const cbg_tile& T, double* chaos) {
+  check_usable(g);
+  int rc = CBG_OK;
+  const int local = step([&] { rc = grid_chaos_device(col_comm(g), T, chaos, g->compute); });
+  return world_chaos(g, std::max(local, rc), chaos);
+}
+
+int grid_inflate(cbg_grid* g, cbg_tile& T, double power, double* chaos) {
+  check_usable(g);
+  int rc = CBG_OK;
+  HipMclStats& hs = hipmcl_stats();
+  hs.inflate_nnz = T.nnz;
+  const int local = step([&] { rc = grid_inflate_device(col_comm(g), T, power, chaos, g->compute, hs.inflate_ms); });
+  return world_chaos(g, std::max(local, rc), chaos);
+}
+
+// the tile's offsets in the gm x gn matrix (SpParMat::Owner, SpParMat.cpp:5068-5097: blocks of
+// ext / np, the last one longer), or false when the tile's shape is not that block's
+static bool tile_place(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, int64_t* roff, int64_t* coff) {
+  *roff = (int64_t)g->prow * (gm / g->pr);
+  *coff = (int64_t)g->pcol * (gn / g->pc);
+  const int64_t m = g->prow == g->pr - 1 ? gm - *roff : gm / g->pr;
+  const int64_t n = g->pcol == g->pc - 1 ? gn - *coff : gn / g->pc;
+  return T.m == m && T.n == n;
+}
+
+// mode 0: RemoveLoops, 1: AddLoops (fix_min: as AdjustLoops calls it)
+static int grid_edit_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, int mode, int replace, int fix_min,
+                           const double* loopvals, cbg_tile& out, int64_t* found) {
+  check_usable(g);
+  int64_t roff = 0, coff = 0;
+  int rc = gm != gn || !tile_place(g, T, gm, gn, &roff, &coff) ? CBG_ERR_DIMMISMATCH : CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  hipStream_t cs = g->compute;
+  TileGuard o;
+  int64_t nf = 0;
+  rc = step([&] {
+    DBuf<double> lv;
+    if (mode == 1) {
+      lv.reset(std::max<int64_t>(T.n, 1));
+      if (T.n) CBG_HIP(hipMemcpyAsync(lv.p, loopvals, sizeof(double) * T.n, hipMemcpyHostToDevice, cs));
+    }
+    tile_edit_loops_device(T, coff - roff, mode, replace, fix_min, lv.p, o.t, &nf, cs);
+    CBG_HIP(hipStreamSynchronize(cs));
+  });
+  if ((rc = agree(g, rc))) return rc;
+  if (found) {
+    if ((rc = agree(g, step([&] { allreduce_sum_i64(g, &nf); })))) return rc;
+    *found = nf;
+  }
+  out = o.release();
+  return CBG_OK;
+}
+
+int grid_remove_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out, int64_t* removed) {
+  return grid_edit_loops(g, T, gm, gn, 0, 0, 0, nullptr, out, removed);
+}
+int grid_add_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const double* loopvals, int replace,
+                   cbg_tile& out) {
+  return grid_edit_loops(g, T, gm, gn, 1, replace, 0, loopvals, out, nullptr);
+}
+int grid_adjust_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out) {
+  TileGuard noloops;
+  int rc = grid_edit_loops(g, T, gm, gn, 0, 0, 0, nullptr, noloops.t, nullptr);
+  if (rc) return rc;
+  std::vector<double> colmax;
+  rc = agree(g, step([&] { colmax.resize((size_t)std::max<int64_t>(T.n, 1)); }));
+  if (rc) return rc;
+  if ((rc = grid_reduce_cols(g, noloops.t, CBG_RED_MAX, std::numeric_limits<double>::min(), colmax.data()))) return rc;
+  return grid_edit_loops(g, noloops.t, gm, gn, 1, 0, 1, colmax.data(), out, nullptr);
+}
+
+// Interpret's connected components: see include/cbg.h.  At the start of a round every
+// rank holds the same labels; a round hooks over the rank's entries, jumps, and takes
+// the minimum over the world.  A round in which no rank lowered a label ends the loop.
+int grid_connected_components(cbg_grid* g, const cbg_tile& T, int64_t gn, int64_t* labels, int64_t* ncomp) {
+  check_usable(g);
+  int64_t roff = 0, coff = 0;
+  int rc = gn < 0 || !tile_place(g, T, gn, gn, &roff, &coff) ? CBG_ERR_DIMMISMATCH : CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  hipStream_t cs = g->compute;
+  const int P = g->nranks;
+  const int64_t n1 = std::max<int64_t>(gn, 1);
+  DBuf<uint64_t> L, all, changed;
+  rc = step([&] {
+    L.reset(n1);
+    changed.reset(1);
+    if (P > 1) all.reset(g->host_mode ? (size_t)n1 * P : (size_t)n1);
+    cc_init_device(L.p, gn, cs);
+    CBG_HIP(hipStreamSynchronize(cs));
+  });
+  if ((rc = agree(g, rc))) return rc;
+  for (int64_t round = 0;; ++round) {
+    uint64_t ch = 0;
+    rc = round > gn ? (int)CBG_ERR_NOTSUPPORTED : step([&] {
+      CBG_HIP(hipMemsetAsync(changed.p, 0, sizeof(uint64_t), cs));
+      cc_round_device(T, roff, coff, L.p, gn, changed.p, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+      if (P > 1 && gn > 0) {
+        if (g->host_mode) {
+          allgather_device(g, COMM_WORLD, L.p, all.p, sizeof(uint64_t) * gn);
+          cc_min_device(L.p, all.p, P, gn, changed.p, cs);
+        } else {
+          CBG_HIP(hipMemcpyAsync(all.p, L.p, sizeof(uint64_t) * gn, hipMemcpyDeviceToDevice, g->comm));
+          CBG_NCCL(ncclAllReduce(all.p, all.p, (size_t)gn, ncclUint64, ncclMin, g->world, g->comm));
+          wait_comm(g);
+          cc_min_device(L.p, all.p, 1, gn, changed.p, cs);
+        }
+      }
+      CBG_HIP(hipMemcpyAsync(&ch, changed.p, sizeof(uint64_t), hipMemcpyDeviceToHost, cs));
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    int64_t any = 0;
+    if ((rc = agree_val(g, rc, ch ? 1 : 0, nullptr, &any))) return rc;
+    if (!any) break;
+  }
+  // canonical labels: the rank of the component's smallest vertex among the smallest vertices
+  int64_t nc = 0;
+  rc = step([&] {
+    std::vector<uint64_t> h((size_t)n1);
+    std::vector<int64_t> rank_of((size_t)n1);
+    if (gn > 0) CBG_HIP(hipMemcpy(h.data(), L.p, sizeof(uint64_t) * gn, hipMemcpyDeviceToHost));
+    for (int64_t v = 0; v < gn; ++v)
+      if (h[v] == (uint64_t)v) rank_of[v] = nc++;
+    for (int64_t v = 0; labels && v < gn; ++v) labels[v] = rank_of[h[v]];
+  });
+  if ((rc = agree(g, rc))) return rc;
+  if (ncomp) *ncomp = nc;
+  return CBG_OK;
+}
+
+int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P, cbg_hipmcl_iter_fn fn,
+                void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters, int64_t* iterations) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  HipMclStats& hs = hipmcl_stats();
+  hs = HipMclStats{};
+  hipStream_t cs = g->compute;
+  const double eps = P.eps > 0 ? P.eps : 1e-4;
+  const cbg_mcl_params& pp = P.prune;
+  const bool pruning = pp.hard_threshold > 0 || pp.select_num > 0 || pp.recover_num > 0 || pp.recover_pct > 0;
+  TileGuard cur;
+  int rc = grid_adjust_loops(g, A, gn, gn, cur.t);
+  if (rc) return rc;
+  if ((rc = grid_make_col_stochastic(g, cur.t))) return rc;
+  int64_t nnz = cur.t.nnz;
+  if ((rc = agree(g, step([&] { allreduce_sum_i64(g, &nnz); })))) return rc;
+  bool pre = P.preprune > 0;
+  if (P.preprune < 0) pre = gn > 0 && nnz / gn > std::max(pp.select_num, pp.recover_num);  // MCL.cpp:531-538
+  if (pre && pruning) {
+    TileGuard pruned;
+    if ((rc = grid_mcl_prune(g, cur.t, &pp, pruned.t))) return rc;
+    cur = std::move(pruned);
+  }
+  double chaos = 1.0;
+  int64_t it = 0;
+  while (chaos > eps && (P.max_iterations == 0 || it < P.max_iterations)) {
+    // the squaring multiplies A by a copy: the SUMMA refuses aliased operands
+    TileGuard B, C;
+    if ((rc = agree(g, step([&] {
+           tile_slice_cols(cur.t, 0, cur.t.n, B.t, cs);
+           CBG_HIP(hipStreamSynchronize(cs));
+         }))))
+      return rc;
+    double prune0 = 0;
+    for (double x : mcl_stats().ms) prune0 += x;
+    const auto t0 = clk::now();
+    rc = pruning ? summa_spgemm_mcl(g, cur.t, B.t, gn, gn, CBG_PLUS_TIMES, P.algo, P.exec, P.phases,
+                                    P.per_process_memory_gb, nullptr, nullptr, &C.t, pp)
+                 : summa_spgemm_phased(g, cur.t, B.t, gn, gn, CBG_PLUS_TIMES, P.algo, P.exec, P.phases,
+                                       P.per_process_memory_gb, nullptr, nullptr, &C.t);
+    if (rc) return rc;
+    const double ms_expand = ms_since(t0);
+    double ms_prune = -prune0;
+    for (double x : mcl_stats().ms) ms_prune += x;
+    B = TileGuard();
+    cur = std::move(C);
+    const auto t1 = clk::now();
+    if ((rc = grid_inflate(g, cur.t, P.inflation, &chaos))) return rc;
+    const double ms_inflate = ms_since(t1);
+    nnz = cur.t.nnz;
+    if ((rc = agree(g, step([&] { allreduce_sum_i64(g, &nnz); })))) return rc;
+    ++it;
+    hs.iterations = it;
+    hs.chaos = chaos;
+    hs.final_nnz = nnz;
+    hs.ms_expand += ms_expand;
+    hs.ms_prune += ms_prune;
+    hs.ms_inflate += ms_inflate;
+    if (fn) fn(user, it, chaos, nnz, ms_expand, ms_prune, ms_inflate);
+  }
+  hs.final_nnz = nnz;
+  hs.chaos = chaos;
+  if (iterations) *iterations = it;
+  if (labels || nclusters)
+    if ((rc = grid_connected_components(g, cur.t, gn, labels, nclusters))) return rc;
+  if (final_local) *final_local = cur.release();
+  return CBG_OK;
 }
 
 }  // namespace cbg

@@ -600,6 +600,37 @@ class SpParMat {
                  "Kselect");
     return kth;
   }
+  // SpParMat::Reduce(Column, op, id[, unop]) as MCL.cpp:392-417 uses it: `what` is
+  // CBG_RED_SUM / MAX / SUMSQ / COUNT; the values of this rank's LOCAL columns over
+  // their whole grid column (id for empty ones).  Collective over the grid.
+  std::vector<double> Reduce(Dim dim, int what, double id) const {
+    if (dim != Column) cbg_abort_on(CBG_ERR_NOTSUPPORTED, "Reduce: columns only");
+    std::vector<double> out((size_t)std::max<int64_t>(spSeq->tile()->n, 1));
+    cbg_abort_on(cbg_grid_reduce_cols(commGrid->handle(), spSeq->tile(), what, id, out.data()), "Reduce");
+    out.resize((size_t)spSeq->tile()->n);
+    return out;
+  }
+  // SpParMat::Apply(bind2nd(exponentiate(), power)) (Operations.h:140-143), in place
+  void ApplyPow(double power) { cbg_abort_on(cbg_tile_apply(spSeq->tile(), CBG_APPLY_POW, power), "Apply"); }
+  // SpParMat::RemoveLoops / AddLoops (SpParMat.cpp:3257-3335); loopvals: the vector's global values
+  IT RemoveLoops() {
+    cbg_tile t{};
+    int64_t removed = 0;
+    cbg_abort_on(cbg_grid_remove_loops(commGrid->handle(), spSeq->tile(), m_, n_, &t, &removed), "RemoveLoops");
+    spSeq->reset(t);
+    return (IT)removed;
+  }
+  void AddLoops(const std::vector<double>& loopvals, bool replaceExisting = false) {
+    if ((int64_t)loopvals.size() != (int64_t)n_) cbg_abort_on(CBG_ERR_DIMMISMATCH, "AddLoops: vector length");
+    const int64_t lo = (int64_t)commGrid->GetRankInProcRow() * ((int64_t)n_ / commGrid->GetGridCols());
+    cbg_tile t{};
+    cbg_abort_on(cbg_grid_add_loops(commGrid->handle(), spSeq->tile(), m_, n_, loopvals.data() + lo, replaceExisting, &t),
+                 "AddLoops");
+    spSeq->reset(t);
+  }
+  void AddLoops(NT loopval, bool replaceExisting = false) {
+    AddLoops(std::vector<double>((size_t)n_, (double)loopval), replaceExisting);
+  }
   // restriction operator (mfiles/genrestrict.m role): n x n/order
   static SpParMat restriction(std::shared_ptr<CommGrid> g, int scale, int order, uint64_t seed = 0x5EED) {
     cbg_tile t{};
@@ -746,6 +777,74 @@ void MCLPruneRecoverySelect(SpParMat<IT, NT, DER>& A, NT hardThreshold, IT selec
   cbg_tile t{};
   cbg_abort_on(cbg_grid_mcl_prune(A.commGrid->handle(), A.spSeq->tile(), &p, &t), "MCLPruneRecoverySelect");
   A.spSeq->reset(t);
+}
+
+// ---- the HipMCL iteration (Applications/MCL.cpp), the reference's signatures ----
+template <typename IT, typename NT, typename DER>
+void MakeColStochastic(SpParMat<IT, NT, DER>& A) {  // MCL.cpp:390-395
+  cbg_abort_on(cbg_grid_make_col_stochastic(A.commGrid->handle(), A.spSeq->tile()), "MakeColStochastic");
+}
+template <typename IT, typename NT, typename DER>
+NT Chaos(SpParMat<IT, NT, DER>& A) {  // MCL.cpp:408-421
+  double c = 0;
+  cbg_abort_on(cbg_grid_chaos(A.commGrid->handle(), A.spSeq->tile(), &c), "Chaos");
+  return (NT)c;
+}
+template <typename IT, typename NT, typename DER>
+void Inflate(SpParMat<IT, NT, DER>& A, double power) {  // MCL.cpp:447-450
+  A.ApplyPow(power);
+}
+template <typename IT, typename NT, typename DER>
+void AdjustLoops(SpParMat<IT, NT, DER>& A) {  // MCL.cpp:464-474
+  cbg_tile t{};
+  cbg_abort_on(cbg_grid_adjust_loops(A.commGrid->handle(), A.spSeq->tile(), A.getnrow(), A.getncol(), &t), "AdjustLoops");
+  A.spSeq->reset(t);
+}
+// Interpret (MCL.cpp:373-386): the cluster of every vertex (all of them, on every rank;
+// the reference returns a FullyDistVec), components numbered by their smallest vertex.
+// A is left unchanged (the reference symmetrises it in place).
+template <typename IT, typename NT, typename DER>
+std::vector<IT> Interpret(SpParMat<IT, NT, DER>& A) {
+  std::vector<int64_t> lab((size_t)std::max<int64_t>(A.getncol(), 1));
+  cbg_abort_on(cbg_grid_connected_components(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), lab.data(), nullptr),
+               "Interpret");
+  return std::vector<IT>(lab.begin(), lab.begin() + A.getncol());
+}
+// the reference's HipMCLParam fields this path reads (MCL.cpp:58-99), its defaults
+struct HipMCLParam {
+  double inflation = 2.0, prunelimit = 1.0 / 10000.0, recover_pct = .9;
+  int64_t select = 1100, recover_num = 1400;
+  int phases = 1, perProcessMem = 0;
+  bool preprune = false;       // forced; otherwise the reference's rule decides (MCL.cpp:531-538)
+  int64_t max_iterations = 0;  // this library's extension: 0 = until chaos <= EPS
+  // filled by HipMCL: iterations run and the chaos of each
+  int iterations = 0;
+  std::vector<double> chaos;
+};
+// HipMCL() (MCL.cpp:515-647), one layer, without RemoveIsolated / RandPermute: the
+// cluster of every vertex.  A is left unchanged (the reference iterates in place).
+template <typename IT, typename NT, typename DER>
+std::vector<IT> HipMCL(SpParMat<IT, NT, DER>& A, HipMCLParam& param) {
+  cbg_hipmcl_params p{};
+  p.inflation = param.inflation;
+  p.prune = {param.prunelimit, param.select, param.recover_num, param.recover_pct};
+  p.phases = param.phases;
+  p.algo = CBG_DOUBLEBUFF;
+  p.exec = CBG_EXEC_PANEL;
+  p.preprune = param.preprune ? 1 : -1;
+  p.per_process_memory_gb = param.perProcessMem;
+  p.max_iterations = param.max_iterations;
+  param.chaos.clear();
+  auto fn = [](void* user, int64_t, double chaos, int64_t, double, double, double) {
+    static_cast<std::vector<double>*>(user)->push_back(chaos);
+  };
+  std::vector<int64_t> lab((size_t)std::max<int64_t>(A.getncol(), 1));
+  int64_t its = 0;
+  cbg_abort_on(cbg_grid_hipmcl(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), &p, fn, &param.chaos, nullptr,
+                               lab.data(), nullptr, &its),
+               "HipMCL");
+  param.iterations = (int)its;
+  return std::vector<IT>(lab.begin(), lab.begin() + A.getncol());
 }
 
 // BlockSpGEMM (BlockSpGEMM.h:14-131): C = A*B block by block, A split into br

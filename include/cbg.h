@@ -373,6 +373,111 @@ enum {
 enum { CBG_MCL_MS_STATS = 0, CBG_MCL_MS_KSELECT = 1, CBG_MCL_MS_COMPACT = 2, CBG_MCL_MS_N = 3 };
 int cbg_last_mcl_stats(int64_t* counts, int n, double* ms);
 
+/* ---------------- HipMCL iteration (Applications/MCL.cpp:515-647) ---------------- */
+/* SpParMat::Reduce(Column, op, id[, unop]) (SpParMat.cpp, as MCL.cpp:392-417 uses it),
+ * collective along the grid column: out[j] (HOST, local->n doubles) = the sum, maximum,
+ * sum of squares or count of local column j over the row blocks of its grid column.
+ * An empty column gives `identity`; CBG_RED_MAX gives max(identity, values), as the
+ * reference folds from id (the sums' id is 0.0 in every reference call: it only fills
+ * empty columns here).  One pass over val yields all four (k_col_moments); a column's
+ * sums depend on its length alone (the order of cbg_tile_col_stats) and the ranks'
+ * partial results are added in rank order: the same bits in every run and on every
+ * rank of the grid column.  The sums start from +0.0 (idle lanes add +0.0), so a column
+ * whose values are all -0.0 sums to +0.0, where a host sum of its values gives -0.0. */
+enum { CBG_RED_SUM = 0, CBG_RED_MAX = 1, CBG_RED_SUMSQ = 2, CBG_RED_COUNT = 3 };
+int cbg_grid_reduce_cols(cbg_grid* g, const cbg_tile* local, int what, double identity, double* out);
+/* upper column length of each column-moment kernel class but the last (16 lanes, a
+ * wave; longer columns: a block): bounds[i] for i < min(n, 2); returns 2 */
+int cbg_mcl_moment_bounds(int64_t* bounds, int n);
+/* SpParMat::Apply (SpParMat.h Apply(unop)), in place on a device tile.  CBG_APPLY_POW is
+ * exponentiate (Operations.h:140-143): arg == 2.0 is computed as v * v (exact; HipMCL's
+ * default inflation), any other arg through the device pow. */
+enum { CBG_APPLY_POW = 0 };
+int cbg_tile_apply(cbg_tile* t, int op, double arg);
+/* MakeColStochastic (MCL.cpp:390-395), in place, collective along the grid column:
+ * inv = (sum == 0) ? DBL_MAX : 1.0 / sum (safemultinv, Operations.h:103-110), then
+ * v * inv: two roundings, like the reference (not v / sum). */
+int cbg_grid_make_col_stochastic(cbg_grid* g, cbg_tile* local);
+/* Chaos (MCL.cpp:408-421): the maximum over the columns of (max(0, values) - sumsq) *
+ * count, folded from 0, then the maximum over the grid.  Collective over the grid. */
+int cbg_grid_chaos(cbg_grid* g, const cbg_tile* local, double* chaos);
+/* The iteration's step after the expansion (MCL.cpp:591-611: MakeColStochastic, Chaos,
+ * Inflate, MakeColStochastic) in three passes over val: 1. column sums; 2. v <- v * inv,
+ * the chaos moments of the scaled values, w = pow(v, power) written back and the column
+ * sums of w; 3. w <- w * inv2; one grid-column combine of the per-column arrays after
+ * passes 1 and 2.  The tile and *chaos are bit-identical to cbg_grid_make_col_stochastic,
+ * cbg_grid_chaos, cbg_tile_apply(CBG_APPLY_POW, power), cbg_grid_make_col_stochastic. */
+int cbg_grid_inflate(cbg_grid* g, cbg_tile* local, double power, double* chaos);
+/* device ms of the last cbg_grid_inflate's three passes on this rank (with several
+ * ranks in a grid column, passes 1 and 2 include the combine) and the entries they ran over */
+int cbg_last_inflate_stats(double* ms3, int64_t* nnz);
+
+/* SpParMat::RemoveLoops / AddLoops(FullyDistVec, replaceExisting) (SpParMat.cpp:3257-3335,
+ * SpTuples.h:113-228) of the gm x gn distributed matrix whose tile is `local`; out = this
+ * rank's new tile (rows ascending, columns that become nonempty enter jc, emptied ones
+ * leave).  The tile's place comes from the grid (SpParMat::Owner, SpParMat.cpp:5068-5097),
+ * so on a non-square grid the off-diagonal tiles the diagonal crosses are handled too
+ * (the reference touches the diagonal processors only).  gm != gn: CBG_ERR_DIMMISMATCH.
+ * *removed (may be NULL): the loops removed over the whole grid.  loopvals: HOST array of
+ * local->n values, the loop of each local column; replace_existing as the reference's. */
+int cbg_grid_remove_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, cbg_tile* out,
+                          int64_t* removed);
+int cbg_grid_add_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, const double* loopvals,
+                       int replace_existing, cbg_tile* out);
+/* AdjustLoops (MCL.cpp:464-474): RemoveLoops, colmaxs = Reduce(Column, max,
+ * numeric_limits<double>::min()), AddLoops(colmaxs).  The reference's quirk is kept: the
+ * Apply at :469 that would turn the isolated vertices' numeric_limits::min() into 1.0
+ * acts on A (where it changes a stored value equal to min() only), not on colmaxs, so
+ * the loop of an empty column is numeric_limits<double>::min(); MakeColStochastic then
+ * makes it 1.0 (min() * (1 / min()) is exact). */
+int cbg_grid_adjust_loops(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, cbg_tile* out);
+
+/* Interpret (MCL.cpp:373-386) with the reference's CC: the connected components of the
+ * gn x gn distributed matrix, every stored entry (i, j) an undirected edge (the
+ * components of A + A^T without building it).  Min-label hooking over the tile's
+ * entries and pointer jumping on a dense label vector of gn entries per rank, one
+ * grid-wide minimum per round, until a round changes nothing (more than gn rounds:
+ * CBG_ERR_NOTSUPPORTED).  labels (HOST, gn int64, the same on every rank): labels[v] =
+ * the rank of v's component when the components are ordered by their smallest vertex
+ * (this library's convention: the reference's numbering follows LACC's internals).
+ * *ncomponents (may be NULL) their number. */
+int cbg_grid_connected_components(cbg_grid* g, const cbg_tile* local, int64_t gn, int64_t* labels,
+                                  int64_t* ncomponents);
+
+/* HipMCL() (MCL.cpp:515-647), one layer: AdjustLoops, MakeColStochastic, the optional
+ * pre-pruning (MCLPruneRecoverySelect), then while chaos > eps: A <- A * A with every
+ * piece pruned (cbg_summa_spgemm_mcl), cbg_grid_inflate; finally the connected
+ * components.  A stays on the device throughout.  RemoveIsolated and RandPermute
+ * (MCL.cpp:477-512) need SpRef indexing and the 3D layers a third grid dimension: out of
+ * scope.  The squaring multiplies A by a device copy of itself (one copy per
+ * iteration): the public SUMMA's refusal of aliased operands stays. */
+typedef struct cbg_hipmcl_params {
+  double inflation;        /* > 0 */
+  cbg_mcl_params prune;    /* hardThreshold, selectNum, recoverNum, recoverPct */
+  int32_t phases;          /* as cbg_summa_spgemm_memeff */
+  int32_t algo, exec;      /* CBG_DOUBLEBUFF / CBG_SYNCH, CBG_EXEC_PANEL / CBG_EXEC_STAGED */
+  int32_t preprune;        /* -1: the reference's rule nnz / nv > max(S, R) (MCL.cpp:531-538); 0, 1: forced */
+  int64_t per_process_memory_gb;
+  double eps;              /* <= 0: 1e-4 (EPS, MCL.cpp:55) */
+  int64_t max_iterations;  /* this library's extension; 0: unlimited, like the reference.  At the cap the
+                              call returns CBG_OK: *iterations and the last chaos tell */
+} cbg_hipmcl_params;
+/* called once per iteration on every rank, after its inflation */
+typedef void (*cbg_hipmcl_iter_fn)(void* user, int64_t iter, double chaos, int64_t nnz, double ms_expand,
+                                   double ms_prune, double ms_inflate);
+/* final_local (may be NULL): this rank's tile of the converged matrix; labels (may be
+ * NULL), *nclusters, *iterations (may be NULL): as cbg_grid_connected_components.
+ * A NaN or non-positive inflation, negative max_iterations or pruning parameters:
+ * CBG_ERR_INVALIDPARAMS before any device work. */
+int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
+                    cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters,
+                    int64_t* iterations);
+/* the last cbg_grid_hipmcl: iterations, the last chaos, the global nnz of the final
+ * matrix, and this rank's summed ms of the expansions (multiply and pruning), of the
+ * pruning inside them (device ms) and of the inflations */
+int cbg_last_hipmcl_stats(int64_t* iterations, double* chaos, int64_t* final_nnz, double* ms_expand,
+                          double* ms_prune, double* ms_inflate);
+
 /* SpParMat::Transpose (SpParMat.cpp:3528-3590), collective over a square grid:
  * out = this rank's tile of the transposed matrix (the transpose of the
  * complement rank's tile, exchanged with RCCL send/recv).  CBG_ERR_NOTSQUARE

@@ -17,6 +17,10 @@ unpruned product (two prunes, equal digests), and the phase independence of the 
 pruned product with exact values ((1 + (7 row + 13 col) % 8) / 16, every sum exact):
 the digests for phases 1, the memory-chosen count and 4 must be equal.  Writes one JSON document (--out, default
 profiles/mcl_bench_s<scale>.json) and prints it.
+
+--iterate runs the whole HipMCL loop instead (AdjustLoops, MakeColStochastic, then the
+pruned squaring and the fused inflation until chaos <= 1e-4) and writes
+profiles/hipmcl_s<scale>.json: see iterate().
 """
 import argparse
 import json
@@ -65,8 +69,45 @@ def run(cbg, A, B, phases, params, digest=True):
                 digest=dict(nnz=acc["nnz"], hs="%016x" % acc["hs"], hv="%016x" % acc["hv"]))
 
 
+def iterate(cbg, A, a):
+    """--iterate: the whole HipMCL loop on the normalised R-MAT.  Per iteration the expand,
+    prune and inflate ms and the nnz; for the inflation's three passes the achieved bytes/s
+    (pass 1 reads 8 B per entry, passes 2 and 3 read 8 B and write 8 B) as a fraction of the
+    copy bandwidth measured in this process."""
+    copy_gbps = cbg.hbm_copy_bandwidth(1 << 30, 10)
+    its = []
+
+    def on_iteration(it, chaos, nnz, ms_expand, ms_prune, ms_inflate):
+        st = cbg.inflate_stats()
+        passes = []
+        for ms, per_entry in zip(st["ms"], (8.0, 16.0, 16.0)):
+            gbps = per_entry * st["nnz"] / ms / 1e6 if ms > 0 else None
+            passes.append(dict(ms=ms, gbps=gbps, fraction_of_copy=gbps / copy_gbps if gbps else None))
+        its.append(dict(iteration=it, chaos=chaos, nnz=nnz, entries_inflated=st["nnz"], expand_ms=ms_expand,
+                        prune_ms=ms_prune, inflate_ms=ms_inflate, inflate_passes=passes))
+
+    t0 = time.perf_counter()
+    labels, n = cbg.HipMCL(A, inflation=a.inflation, prunelimit=a.threshold, select=a.select, recover_num=a.recover,
+                           recover_pct=a.pct, phases=a.phases, max_iterations=a.max_iterations,
+                           on_iteration=on_iteration)
+    wall = (time.perf_counter() - t0) * 1e3
+    out = dict(scale=a.scale, ef=a.ef, inflation=a.inflation,
+               params=dict(hardThreshold=a.threshold, selectNum=a.select, recoverNum=a.recover, recoverPct=a.pct),
+               iterations=n, clusters=int(labels.max()) + 1 if len(labels) else 0, wall_ms=wall,
+               hbm_copy_gbps=copy_gbps, moment_bounds=cbg.mcl_moment_bounds(), totals=cbg.hipmcl_stats(),
+               per_iteration=its)
+    path = a.out or os.path.join(REPO, "profiles", "hipmcl_s%d.json" % a.scale)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--iterate", action="store_true", help="run the whole HipMCL loop (profiles/hipmcl_s<scale>.json)")
+    ap.add_argument("--inflation", type=float, default=2.0)
+    ap.add_argument("--max-iterations", type=int, default=0)
     ap.add_argument("--scale", type=int, default=20)
     ap.add_argument("--ef", type=int, default=16)
     ap.add_argument("--phases", type=int, default=-1, help="-1: from the device's free memory")
@@ -83,6 +124,8 @@ def main():
     A = cbg.SpParMat.rmat(g, a.scale, a.ef)
     cnt, tot = A.tile.col_stats(-1.0, 1)  # column sums (the statistics kernel itself)
     A.tile.dim_apply(cbg.Column, np.where(tot > 0, 1.0 / np.maximum(tot, 1e-300), 1.0), "multiplies")
+    if a.iterate:
+        return iterate(cbg, A, a)
     B = A.copy()
     params = (a.threshold, a.select, a.recover, a.pct)
     copy_gbps = cbg.hbm_copy_bandwidth(1 << 30, 10)
