@@ -290,7 +290,10 @@ class Tile:
         return t
 
     def dim_apply(self, dim, vec, op="multiplies"):
-        """SpParMat::DimApply on this tile (in place): vec has n (Column) or m (Row) values."""
+        """SpParMat::DimApply on this tile (in place): vec has n (Column) or m (Row) values.
+        op: "multiplies", "plus", "min", "max"; min and max are the reference's minimum(x, v) =
+        x < v ? x : v and maximum(x, v) = x < v ? v : x (Operations.h:153-179), not fmin / fmax:
+        with a NaN on either side, or +0.0 against -0.0, min gives v and max the value x."""
         v = np.ascontiguousarray(vec, np.float64)
         if len(v) != (self.n if dim == Column else self.m):
             raise CbgError(INVALIDPARAMS, "DimApply vector length does not match the tile")
@@ -908,7 +911,9 @@ class SpParMat:
 
     def DimApply(self, dim, vec, op="multiplies"):
         """SpParMat::DimApply (SpParMat.cpp:801) with a dense global vector (host array of
-        ncol (Column) or nrow (Row) values); each rank applies its block's slice."""
+        ncol (Column) or nrow (Row) values); each rank applies its block's slice.  "min" and
+        "max" compare like the reference's minimum / maximum (x < v ? x : v, x < v ? v : x;
+        see Tile.dim_apply), not like fmin / fmax."""
         total, parts, idx = ((self.gn, self.grid.grid_cols, self.grid.pcol) if dim == Column
                              else (self.gm, self.grid.grid_rows, self.grid.prow))
         lo, hi = block_range(total, parts, idx)

@@ -95,7 +95,11 @@ void tile_transpose(const cbg_tile& T, cbg_tile& out, hipStream_t s) {
   keys_to_tile(k0.p, v0.p, n, T.n, T.m, out, s);
 }
 
-// dim 0 (Column): x(i,j) op= v[j];  dim 1 (Row): x(i,j) op= v[i]
+// dim 0 (Column): x(i,j) op= v[j];  dim 1 (Row): x(i,j) op= v[i].  min and max are
+// the reference's minimum / maximum (Operations.h:153-179), a < b ? a : b and
+// a < b ? b : a with a the matrix value and b the scaler, not fmin / fmax: when the
+// comparison is false (a NaN on either side, +0.0 against -0.0) min gives the scaler
+// and max the value
 __global__ void k_dim_apply(int64_t nzc, const int64_t* __restrict__ cp, const int32_t* __restrict__ jc,
                             const int32_t* __restrict__ ir, double* __restrict__ val, const double* __restrict__ v,
                             int dim, int op) {
@@ -105,7 +109,7 @@ __global__ void k_dim_apply(int64_t nzc, const int64_t* __restrict__ cp, const i
   for (int64_t q = cp[i] + lane_id(); q < cp[i + 1]; q += WAVE) {
     const double b = dim == 0 ? vc : v[ir[q]];
     const double a = val[q];
-    val[q] = op == 0 ? a * b : op == 1 ? a + b : op == 2 ? fmin(a, b) : fmax(a, b);
+    val[q] = op == 0 ? a * b : op == 1 ? a + b : op == 2 ? (a < b ? a : b) : (a < b ? b : a);
   }
 }
 

@@ -65,10 +65,16 @@ enum Dim { Column = 0, Row = 1 };  // SpDefs.h
 template <class T> struct multiplies { static const int code = CBG_OP_MULTIPLIES; T operator()(T a, T b) const { return a * b; } };
 template <class T> struct plus { static const int code = CBG_OP_PLUS; T operator()(T a, T b) const { return a + b; } };
 
-// Operations.h maximum<T> (the BinOp MultTest passes to ParallelReadMM)
+// Operations.h maximum<T> (the BinOp MultTest passes to ParallelReadMM) and minimum<T>
 template <class T>
 struct maximum {
+  static const int code = CBG_OP_MAX;
   T operator()(const T& a, const T& b) const { return a < b ? b : a; }
+};
+template <class T>
+struct minimum {
+  static const int code = CBG_OP_MIN;
+  T operator()(const T& a, const T& b) const { return a < b ? a : b; }
 };
 
 template <class T1, class T2>
@@ -559,7 +565,10 @@ class SpParMat {
     std::swap(m_, n_);
   }
   // SpParMat::DimApply (SpParMat.cpp:801) with the distributed vector's global
-  // values (FullyDistVec is not on this path); op: a functor class below
+  // values (FullyDistVec is not on this path); op: a functor class with a `code`
+  // (multiplies, plus, minimum, maximum).  minimum and maximum run on the device as
+  // Operations.h:153-179 defines them, x < v ? x : v and x < v ? v : x with x the
+  // matrix value, not as fmin / fmax (NaN and +-0.0 follow the comparison)
   template <typename Op>
   void DimApply(Dim dim, const std::vector<double>& global, Op) {
     const int parts = dim == Column ? commGrid->GetGridCols() : commGrid->GetGridRows();

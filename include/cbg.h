@@ -126,7 +126,11 @@ int cbg_tile_equal(const cbg_tile* a, const cbg_tile* b, double epsilon, int* eq
 int cbg_tile_transpose(const cbg_tile* t, cbg_tile* out);
 /* SpParMat::DimApply (SpParMat.cpp:801): dim CBG_DIM_COLUMN: x(i,j) = op(x(i,j), vec[j]);
  * CBG_DIM_ROW: x(i,j) = op(x(i,j), vec[i]); vec is HOST memory of t->n (t->m) values,
- * the tile's slice of the distributed dense vector.  In place. */
+ * the tile's slice of the distributed dense vector.  In place.
+ * CBG_OP_MIN and CBG_OP_MAX are the reference's minimum and maximum (Operations.h:153-179):
+ * x < v ? x : v and x < v ? v : x with x the matrix value and v the vector's, not fmin / fmax.
+ * Where the comparison is false -- either side NaN, +0.0 against -0.0 -- MIN returns the
+ * vector's value and MAX the matrix value, bit for bit. */
 enum { CBG_DIM_COLUMN = 0, CBG_DIM_ROW = 1 };
 enum { CBG_OP_MULTIPLIES = 0, CBG_OP_PLUS = 1, CBG_OP_MIN = 2, CBG_OP_MAX = 3 };
 int cbg_tile_dim_apply(cbg_tile* t, int dim, const double* vec, int op);
