@@ -88,6 +88,8 @@ EXPORTS = [
     "cbg_grid_reduce_cols", "cbg_mcl_moment_bounds", "cbg_tile_apply", "cbg_grid_make_col_stochastic", "cbg_grid_chaos",
     "cbg_grid_inflate", "cbg_last_inflate_stats", "cbg_grid_remove_loops", "cbg_grid_add_loops", "cbg_grid_adjust_loops",
     "cbg_grid_connected_components", "cbg_grid_hipmcl", "cbg_last_hipmcl_stats",
+    "cbg_tile_spref", "cbg_grid_spref", "cbg_rand_perm", "cbg_spref_sort_bounds", "cbg_last_spref_stats",
+    "cbg_grid_hipmcl_prepared", "cbg_grid_nonisolated",
 ]
 RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT = 0, 1, 2, 3  # cbg_grid_reduce_cols
 _REDS = {"sum": RED_SUM, "plus": RED_SUM, "max": RED_MAX, "maximum": RED_MAX, "sumsq": RED_SUMSQ, "count": RED_COUNT}
@@ -101,6 +103,12 @@ class CHipMclParams(ctypes.Structure):
                 ("per_process_memory_gb", ctypes.c_int64), ("eps", ctypes.c_double), ("max_iterations", ctypes.c_int64)]
 
 
+class CHipMclPrep(ctypes.Structure):
+    """cbg_hipmcl_prep (include/cbg.h)"""
+    _fields_ = [("remove_isolated", ctypes.c_int32), ("randpermute", ctypes.c_int32), ("perm_seed", ctypes.c_uint64)]
+
+
+PERM_SEED = 0x5EED  # HipMCL(randpermute=True) default
 # void (*cbg_hipmcl_iter_fn)(void* user, int64 iter, double chaos, int64 nnz, double ms_expand, ms_prune, ms_inflate)
 HIPMCL_ITER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double)
@@ -201,6 +209,15 @@ def lib():
                              ctypes.POINTER(i64)], i32),
         "cbg_last_hipmcl_stats": ([ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
                                   + [ctypes.POINTER(ctypes.c_double)] * 3, i32),
+        "cbg_tile_spref": ([T, vp, i64, vp, i64, T], i32),
+        "cbg_grid_spref": ([vp, T, i64, i64, vp, i64, vp, i64, T], i32),
+        "cbg_rand_perm": ([i64, ctypes.c_uint64, vp], i32),
+        "cbg_spref_sort_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_last_spref_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_grid_nonisolated": ([vp, T, i64, vp, ctypes.POINTER(i64)], i32),
+        "cbg_grid_hipmcl_prepared": ([vp, T, i64, ctypes.POINTER(CHipMclParams), ctypes.POINTER(CHipMclPrep),
+                                      HIPMCL_ITER_FN, vp, T, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp,
+                                      ctypes.POINTER(i64)], i32),
     }
     experiment = "CBG_LIB" in os.environ  # an older build under A/B may lack the newest entry points
     for name, (args, res) in sig.items():
@@ -216,6 +233,18 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise CbgError(rc, lib().cbg_last_error().decode(errors="replace"))
+
+
+def _index_arg(idx, count=None):
+    """an index vector for the C ABI: (None, 0) for "all", else a contiguous int64 array of at
+    least one element (so its address is never NULL) and its length (`count` overrides it)"""
+    if idx is None:
+        return None, 0
+    a = np.ascontiguousarray(idx, np.int64).ravel()
+    n = len(a) if count is None else int(count)
+    if len(a) == 0:
+        a = np.zeros(1, np.int64)
+    return a, n
 
 
 # --------------------------------------------------------------------------
@@ -320,6 +349,16 @@ class Tile:
         thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, np.float64), (self.n,)))
         t = Tile()
         _check(lib().cbg_tile_prune_column(ctypes.byref(self.c), thr.ctypes.data, ctypes.byref(t.c)))
+        return t
+
+    def spref(self, ri=None, ci=None):
+        """SpDCCols::operator()(ri, ci) (SpDCCols.cpp:1355-1383): out(i, j) = self(ri[i], ci[j]) -> new tile;
+        values keep their bits.  None: all rows (columns) in order; an empty list: an extent of 0."""
+        ri, nri = _index_arg(ri)
+        ci, nci = _index_arg(ci)
+        t = Tile()
+        _check(lib().cbg_tile_spref(ctypes.byref(self.c), ri.ctypes.data if ri is not None else None, nri,
+                                    ci.ctypes.data if ci is not None else None, nci, ctypes.byref(t.c)))
         return t
 
     def split_cols(self, cut):
@@ -1015,6 +1054,33 @@ class SpParMat:
         _check(lib().cbg_grid_adjust_loops(self.grid.h, ctypes.byref(self.tile.c), self.gm, self.gn, ctypes.byref(t.c)))
         self._swap(t)
 
+    def SubsRef(self, ri=None, ci=None, inplace=False):
+        """SpParMat::operator()(ri, ci, inplace) / SubsRef_SR (SpParMat.cpp:2026-2247): the matrix
+        B(i, j) = A(ri[i], ci[j]) on the same grid in the standard block layout.  ri / ci: global
+        index vectors, the same on every rank; None: all, in order.  The entries are moved on the
+        device (no selection-matrix products); values keep their bits.  Collective."""
+        ri, nri = _index_arg(ri)
+        ci, nci = _index_arg(ci)
+        t = Tile()
+        _check(lib().cbg_grid_spref(self.grid.h, ctypes.byref(self.tile.c), self.gm, self.gn,
+                                    ri.ctypes.data if ri is not None else None, nri,
+                                    ci.ctypes.data if ci is not None else None, nci, ctypes.byref(t.c)))
+        gm, gn = (nri if ri is not None else self.gm), (nci if ci is not None else self.gn)
+        if inplace:
+            self._swap(t)
+            self.gm, self.gn = gm, gn
+            return self
+        return SpParMat(t, self.grid, gm, gn)
+
+    __call__ = SubsRef
+
+    def LoadImbalance(self):
+        """SpParMat::LoadImbalance (SpParMat.cpp:744-756): the largest tile's nnz times the number of
+        ranks over the global nnz (1.0: balanced).  Collective."""
+        total = self.getnnz()
+        most = self.grid.allreduce_max(float(self.tile.nnz))
+        return most * self.grid.nranks / total if total else 1.0
+
     def copy(self):
         """deep copy (the reference's copy constructor)."""
         a, b = self.tile.split_cols(self.tile.n)
@@ -1282,6 +1348,47 @@ def hipmcl_stats():
                 ms_prune=ms[1].value, ms_inflate=ms[2].value)
 
 
+def rand_perm(n, seed):
+    """this library's RandPerm (cbg_rand_perm): the stable argsort of
+    mix64(seed ^ (i * 0x9E3779B97F4A7C15)), i < n; the same on every rank."""
+    p = np.zeros(max(int(n), 1), np.int64)
+    _check(lib().cbg_rand_perm(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, p.ctypes.data))
+    return p[:int(n)]
+
+
+def spref_sort_bounds():
+    """upper column length of each class of SubsRef's column sort but the last (cbg_spref_sort_bounds)"""
+    b = (ctypes.c_int64 * 2)()
+    n = lib().cbg_spref_sort_bounds(b, 2)
+    return [int(x) for x in b[:n]]
+
+
+def spref_stats():
+    """the last Tile.spref / SubsRef (or HipMCL with preparation steps) on this rank (cbg_last_spref_stats)"""
+    c, ms = (ctypes.c_int64 * 7)(), (ctypes.c_double * 3)()
+    lib().cbg_last_spref_stats(c, 7, ms)
+    return dict(entries_in=int(c[0]), entries_out=int(c[1]), sorted_wave=int(c[2]), sorted_lds=int(c[3]),
+                sorted_radix=int(c[4]), cols_monotone=int(c[5]), bytes_recv=int(c[6]), ms_col=ms[0], ms_row=ms[1],
+                ms_sort=ms[2])
+
+
+def RemoveIsolated(A):
+    """RemoveIsolated (MCL.cpp:476-493): A(nonisov, nonisov) with nonisov the vertices whose column
+    sum is > 0 -> (the new matrix, nonisov).  A vertex with in-edges only leaves with its row."""
+    ids, n = np.zeros(max(A.gn, 1), np.int64), ctypes.c_int64()
+    _check(lib().cbg_grid_nonisolated(A.grid.h, ctypes.byref(A.tile.c), A.gn, ids.ctypes.data, ctypes.byref(n)))
+    nonisov = ids[:n.value].copy()
+    return A.SubsRef(nonisov, nonisov), nonisov
+
+
+def RandPermute(A, seed=PERM_SEED):
+    """RandPermute (MCL.cpp:496-512): A(p, p) with p = rand_perm(n, seed) -> (the new matrix, p)"""
+    if A.gm != A.gn:
+        raise CbgError(DIMMISMATCH, "RandPermute needs a square matrix")
+    p = rand_perm(A.gn, seed)
+    return A.SubsRef(p, p), p
+
+
 def Interpret(A):
     """Interpret (MCL.cpp:373-386): the connected components of A + A^T (not built) ->
     labels[v] = the rank of v's component, components ordered by their smallest vertex."""
@@ -1294,12 +1401,17 @@ def Interpret(A):
 
 def HipMCL(A, inflation=2.0, prunelimit=1e-4, select=1100, recover_num=1400, recover_pct=0.9, phases=1,
            perProcessMem=0, preprune=None, max_iterations=0, on_iteration=None, eps=0.0, algo=DOUBLEBUFF,
-           exec_mode=EXEC_PANEL, keep_final=False):
+           exec_mode=EXEC_PANEL, keep_final=False, remove_isolated=False, randpermute=False, perm_seed=PERM_SEED,
+           return_work_ids=False):
     """HipMCL() (MCL.cpp:515-647) on device: returns (labels, iterations); A is left
     unchanged.  preprune None: the reference's rule (average degree > max(S, R)).
     on_iteration(iter, chaos, nnz, ms_expand, ms_prune, ms_inflate) once per iteration.
     max_iterations > 0 stops there (hipmcl_stats()["chaos"] tells whether it converged).
-    keep_final: also returns the converged matrix, (labels, iterations, SpParMat)."""
+    keep_final: also returns the converged matrix, (labels, iterations, SpParMat).
+    remove_isolated / randpermute: RemoveIsolated and RandPermute(perm_seed) first (MCL.cpp:517-521,
+    cbg_grid_hipmcl_prepared); the labels stay in A's vertex numbering, a removed vertex is a cluster
+    of its own, and the converged matrix is in the working numbering.  return_work_ids: the original
+    vertex of every working vertex is appended to the result."""
     p = CHipMclParams(float(inflation), CMclParams(float(prunelimit), int(select), int(recover_num), float(recover_pct)),
                       int(phases), algo, exec_mode, -1 if preprune is None else int(bool(preprune)), int(perProcessMem),
                       float(eps), int(max_iterations))
@@ -1315,14 +1427,25 @@ def HipMCL(A, inflation=2.0, prunelimit=1e-4, select=1100, recover_num=1400, rec
     labels = np.zeros(max(A.gn, 1), np.int64)
     nc, its = ctypes.c_int64(), ctypes.c_int64()
     final = Tile()
-    _check(lib().cbg_grid_hipmcl(A.grid.h, ctypes.byref(A.tile.c), A.gn, ctypes.byref(p), cb, None,
-                                 ctypes.byref(final.c) if keep_final else None, labels.ctypes.data, ctypes.byref(nc),
-                                 ctypes.byref(its)))
+    work, nw = np.arange(max(A.gn, 1), dtype=np.int64), ctypes.c_int64(A.gn)
+    if remove_isolated or randpermute:
+        prep = CHipMclPrep(int(bool(remove_isolated)), int(bool(randpermute)), int(perm_seed) & 0xFFFFFFFFFFFFFFFF)
+        _check(lib().cbg_grid_hipmcl_prepared(A.grid.h, ctypes.byref(A.tile.c), A.gn, ctypes.byref(p), ctypes.byref(prep),
+                                              cb, None, ctypes.byref(final.c) if keep_final else None,
+                                              labels.ctypes.data, ctypes.byref(nc), ctypes.byref(its), work.ctypes.data,
+                                              ctypes.byref(nw)))
+    else:
+        _check(lib().cbg_grid_hipmcl(A.grid.h, ctypes.byref(A.tile.c), A.gn, ctypes.byref(p), cb, None,
+                                     ctypes.byref(final.c) if keep_final else None, labels.ctypes.data, ctypes.byref(nc),
+                                     ctypes.byref(its)))
     if errors:
         raise errors[0]
+    res = (labels[:A.gn], int(its.value))
     if keep_final:
-        return labels[:A.gn], int(its.value), SpParMat(final, A.grid, A.gn, A.gn)
-    return labels[:A.gn], int(its.value)
+        res += (SpParMat(final, A.grid, nw.value, nw.value),)
+    if return_work_ids:
+        res += (work[:nw.value].copy(),)
+    return res
 
 
 def write_clusters(path, labels):

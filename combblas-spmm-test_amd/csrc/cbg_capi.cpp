@@ -44,6 +44,13 @@ int grid_adjust_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cb
 int grid_connected_components(cbg_grid* g, const cbg_tile& T, int64_t gn, int64_t* labels, int64_t* ncomp);
 int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P, cbg_hipmcl_iter_fn fn,
                 void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters, int64_t* iterations);
+int grid_spref(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
+               const int64_t* ci, int64_t nci, cbg_tile& out);
+void rand_perm(int64_t n, uint64_t seed, int64_t* p);
+int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids);
+int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
+                         const cbg_hipmcl_prep& prep, cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local,
+                         int64_t* labels, int64_t* nclusters, int64_t* iterations, int64_t* work_ids, int64_t* n_work);
 }  // namespace cbg
 
 namespace {
@@ -756,10 +763,8 @@ int cbg_grid_connected_components(cbg_grid* g, const cbg_tile* local, int64_t gn
   return grid_call(g, arg, [&] { return cbg::grid_connected_components(g, *local, gn, labels, ncomponents); });
 }
 
-int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
-                    cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters,
-                    int64_t* iterations) {
-  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+// the argument checks of cbg_grid_hipmcl (and cbg_grid_hipmcl_prepared), before any device work
+static int hipmcl_args(const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params) {
   int arg = check_tile(A_local, true, "A");
   if (!arg && !params) arg = fail(CBG_ERR_INVALIDPARAMS, "params is NULL");
   if (!arg && gn < 0) arg = fail(CBG_ERR_INVALIDPARAMS, "gn is negative");
@@ -772,11 +777,123 @@ int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_
                (params->exec != CBG_EXEC_PANEL && params->exec != CBG_EXEC_STAGED)))
     arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_hipmcl: eps is NaN, or preprune, algo or exec is out of range");
   if (!arg && A_local->nnz + A_local->n >= INT32_MAX) arg = fail(CBG_ERR_NOTSUPPORTED, "A tiles need nnz < 2^31");
+  return arg;
+}
+
+int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
+                    cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters,
+                    int64_t* iterations) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = hipmcl_args(A_local, gn, params);
   return grid_call(g, arg, [&] {
     cbg::thread_stats() = cbg::LocalStats{};
     cbg::merge_stats() = cbg::MergeStats{};
     cbg::mcl_stats() = cbg::MclStats{};
     return cbg::grid_hipmcl(g, *A_local, gn, *params, fn, user, final_local, labels, nclusters, iterations);
+  });
+}
+
+// ---------------- sparse indexing ----------------
+int cbg_grid_info(const cbg_grid* g, int* rank, int* nranks, int* rows, int* cols, int* prow, int* pcol);
+static int index_args(const char* what, const int64_t* idx, int64_t n, int64_t ext) {
+  if (!idx) return CBG_OK;
+  if (n < 0) return fail(CBG_ERR_INVALIDPARAMS, std::string("a negative number of ") + what + " indices");
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || idx[i] >= ext) return fail(CBG_ERR_INVALIDPARAMS, std::string("a ") + what + " index outside the matrix");
+  return CBG_OK;
+}
+
+int cbg_tile_spref(const cbg_tile* t, const int64_t* ri, int64_t nri, const int64_t* ci, int64_t nci, cbg_tile* out) {
+  if (int rc = check_tile(t, true, "tile")) return rc;
+  if (!out) return fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
+  if (int rc = index_args("row", ri, nri, t->m)) return rc;
+  if (int rc = index_args("column", ci, nci, t->n)) return rc;
+  if ((ri && nri >= INT32_MAX) || (ci && nci >= INT32_MAX))
+    return fail(CBG_ERR_NOTSUPPORTED, "the new tile has 2^31 or more rows or columns");
+  return guard([&] {
+    cbg::spref_stats() = cbg::SprefStats{};
+    cbg::tile_spref(*t, ri, nri, ci, nci, *out, default_stream());
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_spref(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
+                   const int64_t* ci, int64_t nci, cbg_tile* out) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && !out) arg = fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
+  if (!arg && (gm < 0 || gn < 0)) arg = fail(CBG_ERR_INVALIDPARAMS, "gm or gn is negative");
+  if (!arg) {  // the tile's place (SpParMat::Owner): blocks of ext / np, the last one longer
+    int pr = 1, pc = 1, prow = 0, pcol = 0;
+    cbg_grid_info(g, nullptr, nullptr, &pr, &pc, &prow, &pcol);
+    const int64_t m = prow == pr - 1 ? gm - (int64_t)prow * (gm / pr) : gm / pr;
+    const int64_t n = pcol == pc - 1 ? gn - (int64_t)pcol * (gn / pc) : gn / pc;
+    if (local->m != m || local->n != n) arg = fail(CBG_ERR_INVALIDPARAMS, "gm x gn does not fit the tile's place in the grid");
+    const int64_t nm = ri ? nri : gm, nn = ci ? nci : gn;
+    if (!arg) arg = index_args("row", ri, nri, gm);
+    if (!arg) arg = index_args("column", ci, nci, gn);
+    if (!arg && (nm - (int64_t)(pr - 1) * (nm / pr) >= INT32_MAX || nn - (int64_t)(pc - 1) * (nn / pc) >= INT32_MAX))
+      arg = fail(CBG_ERR_NOTSUPPORTED, "a new local block has 2^31 or more rows or columns");
+  }
+  // every check above precedes any device work; the code is agreed over the grid
+  return grid_call(g, arg, [&] {
+    cbg::spref_stats() = cbg::SprefStats{};
+    return cbg::grid_spref(g, *local, gm, gn, ri, nri, ci, nci, *out);
+  });
+}
+
+int cbg_rand_perm(int64_t n, uint64_t seed, int64_t* p) {
+  if (n < 0 || (n > 0 && !p)) return fail(CBG_ERR_INVALIDPARAMS, "cbg_rand_perm: n >= 0 and p is needed");
+  return guard([&] {
+    cbg::rand_perm(n, seed, p);
+    return CBG_OK;
+  });
+}
+
+int cbg_spref_sort_bounds(int64_t* bounds, int n) { return cbg::spref_sort_bounds(bounds, n); }
+
+int cbg_last_spref_stats(int64_t* counts, int n, double* ms) {
+  const cbg::SprefStats& m = cbg::spref_stats();
+  for (int i = 0; counts && i < n && i < CBG_SPREF_N; ++i) counts[i] = m.counts[i];
+  for (int i = 0; ms && i < CBG_SPREF_MS_N; ++i) ms[i] = m.ms[i];
+  return CBG_SPREF_N;
+}
+
+int cbg_grid_nonisolated(cbg_grid* g, const cbg_tile* local, int64_t gn, int64_t* ids, int64_t* n) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(local, true, "tile");
+  if (!arg && (gn < 0 || !n || (gn > 0 && !ids))) arg = fail(CBG_ERR_INVALIDPARAMS, "gn >= 0, ids and n are needed");
+  return grid_call(g, arg, [&] {
+    std::vector<int64_t> v;
+    const int rc = cbg::grid_nonisolated(g, *local, gn, v);
+    if (rc) return rc;
+    std::copy(v.begin(), v.end(), ids);
+    *n = (int64_t)v.size();
+    return (int)CBG_OK;
+  });
+}
+
+int cbg_grid_hipmcl_prepared(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
+                             const cbg_hipmcl_prep* prep, cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local,
+                             int64_t* labels, int64_t* nclusters, int64_t* iterations, int64_t* work_ids,
+                             int64_t* n_work) {
+  if (!prep || (!prep->remove_isolated && !prep->randpermute)) {
+    const int rc = cbg_grid_hipmcl(g, A_local, gn, params, fn, user, final_local, labels, nclusters, iterations);
+    if (rc == CBG_OK) {
+      for (int64_t v = 0; work_ids && v < gn; ++v) work_ids[v] = v;
+      if (n_work) *n_work = gn;
+    }
+    return rc;
+  }
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = hipmcl_args(A_local, gn, params);
+  return grid_call(g, arg, [&] {
+    cbg::thread_stats() = cbg::LocalStats{};
+    cbg::merge_stats() = cbg::MergeStats{};
+    cbg::mcl_stats() = cbg::MclStats{};
+    cbg::spref_stats() = cbg::SprefStats{};
+    return cbg::grid_hipmcl_prepared(g, *A_local, gn, *params, *prep, fn, user, final_local, labels, nclusters,
+                                     iterations, work_ids, n_work);
   });
 }
 

@@ -363,6 +363,37 @@ struct HipMclStats {
 };
 HipMclStats& hipmcl_stats();
 
+// sparse indexing B(i, j) = A(ri[i], ci[j]) (cbg_spref.hip)
+struct SprefStats {
+  int64_t counts[CBG_SPREF_N] = {};
+  double ms[CBG_SPREF_MS_N] = {};
+};
+SprefStats& spref_stats();  // the calling thread's; reset by the C ABI's indexing entry points
+int spref_sort_bounds(int64_t* bounds, int n);
+bool spref_strictly_increasing(const int64_t* v, int64_t n);
+// column stage: len[j] = the stored length of global column sel[j] (device ids), from np
+// blocks of `stride` column counts (blocks of `per` columns, the last longer); then the
+// columns rank q owns copied from its tile to the offsets ocp[j]
+void spref_sel_lengths(const int64_t* sel, int64_t nsel, const int32_t* cnt, int64_t stride, int64_t per, int np,
+                       int64_t* len, hipStream_t s);
+void spref_sel_copy(const cbg_tile& src, int q, int64_t per, int np, const int64_t* sel, int64_t nsel,
+                    const int64_t* ocp, int32_t* oir, double* oval, hipStream_t s);
+// dense offsets cp[0 .. ncols] of the columns ids[] (NULL: 0, 1, ...) -> a DCSC tile that takes over ir and val
+void spref_compact(int64_t m, int64_t n, const int32_t* ids, int64_t ncols, const int64_t* cp, DBuf<int32_t>& ir,
+                   DBuf<double>& val, int64_t nnz, cbg_tile& out, hipStream_t s);
+// row stage: the inverse of ri (HOST, n new rows asking for old global rows < gm), and a tile whose
+// rows are the old rows row0 ... expanded to the new rows (new_m of them), columns left unsorted
+struct RowInverse {
+  DBuf<int32_t> cnt, list;
+  DBuf<int64_t> start;
+};
+void spref_build_inverse(const int64_t* ri_host, int64_t n, int64_t gm, RowInverse& inv, hipStream_t s);
+void spref_expand_rows(const cbg_tile& X, int64_t row0, const RowInverse& inv, int64_t new_m, cbg_tile& out,
+                       hipStream_t s);
+void spref_sort_columns(cbg_tile& t, hipStream_t s);  // rows ascending in every column, in place
+void tile_spref(const cbg_tile& T, const int64_t* ri, int64_t nri, const int64_t* ci, int64_t nci, cbg_tile& out,
+                hipStream_t s);
+
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);
 void store_probe(int64_t bytes, int width);

@@ -1786,6 +1786,325 @@ int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_par
   return CBG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// SpParMat::SubsRef_SR (SpParMat.cpp:2026-2247): B(i, j) = A(ri[i], ci[j]) of a
+// distributed matrix (kernels in cbg_spref.hip).  The reference multiplies by
+// two selection matrices; here the entries move.  Columns first, along the grid
+// row: whole stored columns are copied, nothing is sorted, and an indexing that
+// shrinks the matrix shrinks it before the row stage, which touches every entry
+// and sorts.  Every rank broadcasts its tile to its grid row; the receiver
+// copies the columns it asked that rank for straight to their final place (the
+// lengths come from an allgather of the column counts, so one tile is held at a
+// time).  Then the rows, along the grid column: every rank broadcasts its
+// column-stage tile, the receiver expands it through the inverse of its slice
+// of ri, the parts are concatenated per column and the columns sorted (not when
+// the slice of ri is strictly increasing: the parts' row ranges ascend).  The
+// column-stage tile is freed before the concatenation: the peak is the gathered
+// block column plus the output.  Agreements as in grid_block_extract.
+// ---------------------------------------------------------------------------
+static void block_span(int64_t ext, int np, int i, int64_t& a, int64_t& b) {
+  const int64_t per = ext / np;
+  a = (int64_t)i * per;
+  b = i == np - 1 ? ext : a + per;
+}
+
+int grid_spref(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
+               const int64_t* ci, int64_t nci, cbg_tile& out) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  check_usable(g);
+  hipStream_t cs = g->compute;
+  SprefStats& st = spref_stats();
+  // the indices themselves were checked by the caller (cbg_grid_spref; RemoveIsolated and RandPermute build valid ones)
+  int64_t roff = 0, coff = 0;
+  int rc = CBG_OK;
+  auto bad = [&](const char* why) {
+    if (step_error().empty()) step_error() = why;
+    return (int)CBG_ERR_INVALIDPARAMS;
+  };
+  if (gm < 0 || gn < 0 || !tile_place(g, T, gm, gn, &roff, &coff)) rc = bad("gm x gn does not fit the tile's place in the grid");
+  if (!rc && ((ri && nri < 0) || (ci && nci < 0))) rc = bad("a negative index count");
+  const int64_t new_m = ri ? nri : gm, new_n = ci ? nci : gn;
+  int64_t U0 = 0, U1 = 0, V0 = 0, V1 = 0;
+  if (!rc) {
+    block_span(new_m, g->pr, g->prow, U0, U1);
+    block_span(new_n, g->pc, g->pcol, V0, V1);
+    // the last blocks are the longest
+    if (new_m - (int64_t)(g->pr - 1) * (new_m / g->pr) >= INT32_MAX || new_n - (int64_t)(g->pc - 1) * (new_n / g->pc) >= INT32_MAX) {
+      if (step_error().empty()) step_error() = "a new local block has 2^31 or more rows or columns";
+      rc = CBG_ERR_NOTSUPPORTED;
+    }
+  }
+  if ((rc = agree(g, rc))) return rc;
+  const bool inject = redist_fault(g);
+  st.counts[CBG_SPREF_ENTRIES_IN] += T.nnz;
+
+  // ---- column stage: X = A(:, ci[V0:V1)) restricted to this rank's old row block
+  TileGuard X;
+  const cbg_tile* src = &T;
+  if (ci) {
+    const auto t0 = clk::now();
+    const int np = g->pc, me = g->pcol;
+    const int64_t per = gn / np, maxn = gn - (int64_t)(np - 1) * per, nsel = V1 - V0;
+    DBuf<int64_t> sel, len, ocp;
+    DBuf<int32_t> mycnt, allcnt, oir;
+    DBuf<double> oval;
+    int64_t nnzX = 0;
+    rc = step([&] {
+      sel.reset(std::max<int64_t>(nsel, 1));
+      len.reset(nsel + 1);
+      ocp.reset(nsel + 1);
+      mycnt.reset(std::max<int64_t>(maxn, 1));
+      allcnt.reset(std::max<int64_t>(maxn, 1) * np);
+      if (nsel) CBG_HIP(hipMemcpyAsync(sel.p, ci + V0, sizeof(int64_t) * nsel, hipMemcpyHostToDevice, cs));
+      tile_counts_device(T, 0, mycnt.p, maxn, cs);
+    });
+    if ((rc = agree(g, rc))) return rc;
+    rc = step([&] {
+      // one rank in the grid row: its own counts (allgather_device would copy them on the null stream,
+      // which the compute stream does not wait for)
+      if (np > 1) allgather_device(g, COMM_ROW, mycnt.p, allcnt.p, sizeof(int32_t) * maxn);
+      spref_sel_lengths(sel.p, nsel, np > 1 ? allcnt.p : mycnt.p, maxn, per, np, len.p, cs);
+      exclusive_scan_i64(len.p, ocp.p, nsel, cs);
+      CBG_HIP(hipMemcpyAsync(&nnzX, ocp.p + nsel, sizeof(int64_t), hipMemcpyDeviceToHost, cs));
+      CBG_HIP(hipStreamSynchronize(cs));
+      oir.reset(std::max<int64_t>(nnzX, 1));
+      oval.reset(std::max<int64_t>(nnzX, 1));
+    });
+    if ((rc = agree(g, rc))) return rc;
+    int64_t e[4];
+    tile_ess(T, e);
+    std::vector<int64_t> E((size_t)4 * np);
+    allgather_i64(g, COMM_ROW, e, E.data(), 4);
+    int local = CBG_OK;
+    for (int q = 0; q < np; ++q) {
+      TileGuard recv;
+      rc = step([&] {
+        if (inject && q == (me + 1) % np) throw HipError("injected fault (CBG_FAULT_INJECT_REDIST) in SubsRef", CBG_ERR_OOM);
+        if (q != me) alloc_like(recv.t, &E[4 * (size_t)q]);
+      });
+      if ((rc = agree(g, rc))) return rc;  // every receive buffer of this broadcast exists
+      cbg_tile bt = T;                     // the root's own tile (bcast_tile does not write it)
+      cbg_tile& sl = q == me ? bt : recv.t;
+      if (q != me) st.counts[CBG_SPREF_BYTES_RECV] += tile_bytes(&E[4 * (size_t)q]);
+      local = std::max(local, step([&] {
+        bcast_group(g, [&] { bcast_tile(g, COMM_ROW, q, &E[4 * (size_t)q], sl, q == me); });
+        wait_comm(g);
+      }));
+      if (!local) local = step([&] { spref_sel_copy(sl, q, per, np, sel.p, nsel, ocp.p, oir.p, oval.p, cs); });
+    }
+    if (!local)
+      local = step([&] {
+        spref_compact(T.m, nsel, nullptr, nsel, ocp.p, oir, oval, nnzX, X.t, cs);
+        CBG_HIP(hipGetLastError());
+      });
+    if ((rc = agree(g, local))) return rc;
+    src = &X.t;
+    st.ms[CBG_SPREF_MS_COL] += ms_since(t0);
+  }
+
+  // ---- row stage: out = X(ri[U0:U1), :) over the grid column's row blocks
+  TileGuard O;
+  if (ri) {
+    const auto t0 = clk::now();
+    const int np = g->pr, me = g->prow;
+    const int64_t per = gm / np, nloc = U1 - U0, ncols = src->n;
+    const bool monotone = spref_strictly_increasing(ri + U0, nloc);
+    RowInverse inv;
+    rc = step([&] { spref_build_inverse(ri + U0, nloc, gm, inv, cs); });
+    if ((rc = agree(g, rc))) return rc;
+    int64_t e[4];
+    tile_ess(*src, e);
+    std::vector<int64_t> E((size_t)4 * np);
+    allgather_i64(g, COMM_COL, e, E.data(), 4);
+    std::vector<TileGuard> parts;
+    int local = CBG_OK;
+    for (int q = 0; q < np; ++q) {
+      TileGuard recv;
+      rc = step([&] {
+        if (inject && !ci && q == (me + 1) % np) throw HipError("injected fault (CBG_FAULT_INJECT_REDIST) in SubsRef", CBG_ERR_OOM);
+        if (q != me) alloc_like(recv.t, &E[4 * (size_t)q]);
+      });
+      if ((rc = agree(g, rc))) return rc;
+      cbg_tile bt = *src;
+      cbg_tile& sl = q == me ? bt : recv.t;
+      if (q != me) st.counts[CBG_SPREF_BYTES_RECV] += tile_bytes(&E[4 * (size_t)q]);
+      local = std::max(local, step([&] {
+        bcast_group(g, [&] { bcast_tile(g, COMM_COL, q, &E[4 * (size_t)q], sl, q == me); });
+        wait_comm(g);
+      }));
+      if (!local)
+        local = step([&] {
+          TileGuard piece;
+          spref_expand_rows(sl, (int64_t)q * per, inv, nloc, piece.t, cs);
+          parts.push_back(std::move(piece));
+        });
+    }
+    X = TileGuard();  // the gathered block column goes before the output is built
+    if (!local)
+      local = step([&] {
+        int64_t total = 0;
+        for (auto& t : parts) total += t.t.nnz;
+        if (parts.size() == 1) {
+          O = std::move(parts[0]);
+        } else if (total == 0) {  // also a block of no columns, which tile_concat_rows has no launch for
+          tile_alloc_device(O.t, nloc, ncols, 0, 0);
+        } else {
+          std::vector<cbg_tile> pv;
+          for (auto& t : parts) pv.push_back(t.t);
+          tile_concat_rows(pv, std::vector<int64_t>(pv.size(), 0), nloc, ncols, O.t, cs);
+        }
+        parts.clear();
+        st.ms[CBG_SPREF_MS_ROW] += ms_since(t0);
+        if (monotone)
+          st.counts[CBG_SPREF_COLS_MONOTONE] += O.t.nzc;
+        else
+          spref_sort_columns(O.t, cs);
+        CBG_HIP(hipStreamSynchronize(cs));
+        CBG_HIP(hipGetLastError());  // a refused launch is this call's failure, not a later one's
+      });
+    if ((rc = agree(g, local))) return rc;
+  } else if (ci) {
+    O = std::move(X);
+  } else {
+    rc = step([&] {
+      tile_slice_cols(T, 0, T.n, O.t, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    if ((rc = agree(g, rc))) return rc;
+  }
+  st.counts[CBG_SPREF_ENTRIES_OUT] += O.t.nnz;
+  out = O.release();
+  return CBG_OK;
+}
+
+// this library's RandPerm: see include/cbg.h
+static uint64_t mix64_host(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+  return z ^ (z >> 31);
+}
+void rand_perm(int64_t n, uint64_t seed, int64_t* p) {
+  std::vector<uint64_t> key((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    key[i] = mix64_host(seed ^ ((uint64_t)i * 0x9E3779B97F4A7C15ULL));
+    p[i] = i;
+  }
+  std::stable_sort(p, p + n, [&](int64_t a, int64_t b) { return key[a] < key[b]; });
+}
+
+// nonisov of RemoveIsolated (MCL.cpp:476-486): the column sums are the same bits on every rank of
+// a grid column; the slices of a grid row, in rank order, are the global list
+int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids) {
+  check_usable(g);
+  int64_t roff = 0, coff = 0;
+  int rc = !tile_place(g, A, gn, gn, &roff, &coff) ? CBG_ERR_DIMMISMATCH : CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  std::vector<double> colsum;
+  rc = step([&] { colsum.resize((size_t)std::max<int64_t>(A.n, 1)); });
+  if ((rc = agree(g, rc))) return rc;
+  if ((rc = grid_reduce_cols(g, A, CBG_RED_SUM, 0.0, colsum.data()))) return rc;
+  const int np = g->pc;
+  std::vector<int64_t> mine, cnts((size_t)np), all;
+  int64_t most = 1;
+  rc = step([&] {
+    for (int64_t j = 0; j < A.n; ++j)
+      if (colsum[j] > 0) mine.push_back(coff + j);
+  });
+  if ((rc = agree(g, rc))) return rc;
+  int64_t cnt = (int64_t)mine.size();
+  allgather_i64(g, COMM_ROW, &cnt, cnts.data(), 1);
+  most = std::max<int64_t>(1, *std::max_element(cnts.begin(), cnts.end()));
+  rc = step([&] {
+    mine.resize((size_t)most, -1);
+    all.resize((size_t)most * np);
+  });
+  if ((rc = agree(g, rc))) return rc;  // every rank holds its buffers before the exchange
+  rc = step([&] {
+    allgather_bytes(g, COMM_ROW, mine.data(), all.data(), sizeof(int64_t) * (size_t)most);
+    ids.clear();
+    for (int q = 0; q < np; ++q)
+      ids.insert(ids.end(), all.begin() + (size_t)q * most, all.begin() + (size_t)q * most + cnts[q]);
+  });
+  return agree(g, rc);
+}
+
+// HipMCL() with its first two steps (MCL.cpp:517-521): RemoveIsolated (:476-493), RandPermute (:496-512)
+int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
+                         const cbg_hipmcl_prep& prep, cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local,
+                         int64_t* labels, int64_t* nclusters, int64_t* iterations, int64_t* work_ids, int64_t* n_work) {
+  check_usable(g);
+  int64_t roff = 0, coff = 0;
+  int rc = !tile_place(g, A, gn, gn, &roff, &coff) ? CBG_ERR_DIMMISMATCH : CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  std::vector<int64_t> ids;  // ids[k] = the original vertex of working vertex k
+  TileGuard W;
+  const cbg_tile* cur = &A;
+  int64_t nw = gn;
+  rc = step([&] {
+    ids.resize((size_t)gn);
+    for (int64_t v = 0; v < gn; ++v) ids[v] = v;
+  });
+  if ((rc = agree(g, rc))) return rc;
+  if (prep.remove_isolated) {
+    if ((rc = grid_nonisolated(g, A, gn, ids))) return rc;
+    nw = (int64_t)ids.size();
+    const int64_t none = 0;  // an empty list is an extent of 0, a NULL pointer would be "all"
+    const int64_t* ip = nw ? ids.data() : &none;
+    TileGuard B;
+    if ((rc = grid_spref(g, *cur, gn, gn, ip, nw, ip, nw, B.t))) return rc;
+    W = std::move(B);
+    cur = &W.t;
+  }
+  if (prep.randpermute) {
+    std::vector<int64_t> p, pid;
+    rc = step([&] {
+      p.resize((size_t)std::max<int64_t>(nw, 1));
+      pid.resize((size_t)nw);
+      rand_perm(nw, prep.perm_seed, p.data());
+      for (int64_t k = 0; k < nw; ++k) pid[k] = ids[p[k]];
+    });
+    if ((rc = agree(g, rc))) return rc;
+    TileGuard B;
+    if ((rc = grid_spref(g, *cur, nw, nw, p.data(), nw, p.data(), nw, B.t))) return rc;
+    W = std::move(B);
+    cur = &W.t;
+    ids.swap(pid);
+  }
+  std::vector<int64_t> wl;
+  const bool want = labels || nclusters;
+  rc = step([&] { wl.resize((size_t)std::max<int64_t>(nw, 1)); });
+  if ((rc = agree(g, rc))) return rc;
+  int64_t nc_work = 0;
+  if ((rc = grid_hipmcl(g, *cur, nw, P, fn, user, final_local, want ? wl.data() : nullptr, want ? &nc_work : nullptr,
+                        iterations)))
+    return rc;
+  if (want) {
+    // back to the original numbering: a working component keeps its vertices, a removed vertex is
+    // a cluster of its own, and the clusters are numbered by their smallest original vertex
+    rc = step([&] {
+      std::vector<int64_t> comp((size_t)std::max<int64_t>(gn, 1), -1), newid((size_t)std::max<int64_t>(nc_work, 1), -1);
+      for (int64_t k = 0; k < nw; ++k) comp[ids[k]] = wl[k];
+      int64_t nc = 0;
+      for (int64_t v = 0; v < gn; ++v) {
+        int64_t l;
+        if (comp[v] < 0) {
+          l = nc++;
+        } else {
+          if (newid[comp[v]] < 0) newid[comp[v]] = nc++;
+          l = newid[comp[v]];
+        }
+        if (labels) labels[v] = l;
+      }
+      if (nclusters) *nclusters = nc;
+    });
+    if ((rc = agree(g, rc))) return rc;
+  }
+  if (work_ids) std::copy(ids.begin(), ids.end(), work_ids);
+  if (n_work) *n_work = nw;
+  return CBG_OK;
+}
+
 }  // namespace cbg
 
 extern "C" int cbg_get_unique_id(void* id) {

@@ -682,6 +682,40 @@ class SpParMat {
     return out;
   }
 
+  // SpParMat::SubsRef_SR / operator()(ri, ci, inplace) (SpParMat.cpp:2026-2247): B(i, j) =
+  // A(ri[i], ci[j]) on the same grid.  ri, ci: global index vectors, the same on every rank (as
+  // Interpret returns them; the reference takes FullyDistVecs).  An empty vector selects nothing
+  // (an extent of 0; the reference spells "all" as an empty vector).  The entries are moved on the
+  // device (cbg_grid_spref), no selection-matrix products; values keep their bits.
+  SpParMat SubsRef_SR(const std::vector<IT>& ri, const std::vector<IT>& ci, bool inplace = false) {
+    const std::vector<int64_t> r(ri.begin(), ri.end()), c(ci.begin(), ci.end());
+    const int64_t none = 0;
+    cbg_tile t{};
+    cbg_abort_on(cbg_grid_spref(commGrid->handle(), spSeq->tile(), m_, n_, r.empty() ? &none : r.data(), (int64_t)r.size(),
+                                c.empty() ? &none : c.data(), (int64_t)c.size(), &t),
+                 "SubsRef_SR");
+    if (inplace) {
+      spSeq->reset(t);
+      m_ = (IT)r.size();
+      n_ = (IT)c.size();
+      return SpParMat(commGrid);
+    }
+    return SpParMat(new DER(t), commGrid, (IT)r.size(), (IT)c.size());
+  }
+  SpParMat operator()(const std::vector<IT>& ri, const std::vector<IT>& ci, bool inplace = false) {
+    return SubsRef_SR(ri, ci, inplace);
+  }
+  // SpParMat::LoadImbalance (SpParMat.cpp:744-756): the largest tile's nnz times the ranks over the global nnz
+  float LoadImbalance() const {
+    int64_t total = spSeq->tile()->nnz;
+    double most = (double)total;
+    int nranks = 1;
+    cbg_abort_on(cbg_grid_info(commGrid->handle(), nullptr, &nranks, nullptr, nullptr, nullptr, nullptr), "LoadImbalance");
+    cbg_abort_on(cbg_grid_allreduce_sum_i64(commGrid->handle(), &total), "LoadImbalance");
+    cbg_abort_on(cbg_grid_allreduce_max(commGrid->handle(), &most), "LoadImbalance");
+    return total ? (float)(most * nranks / (double)total) : 1.0f;
+  }
+
   // SpParMat::operator== (SpParMat.cpp:2878-2884): local equality, AND over the grid
   bool operator==(const SpParMat& rhs) const {
     int64_t bad = (*spSeq == *rhs.spSeq) ? 0 : 1;
@@ -819,6 +853,28 @@ std::vector<IT> Interpret(SpParMat<IT, NT, DER>& A) {
                "Interpret");
   return std::vector<IT>(lab.begin(), lab.begin() + A.getncol());
 }
+// RemoveIsolated (MCL.cpp:476-493), in place: A(nonisov, nonisov) with nonisov the vertices whose
+// column sum is > 0; returns nonisov (the reference prints their number)
+template <typename IT, typename NT, typename DER>
+std::vector<IT> RemoveIsolated(SpParMat<IT, NT, DER>& A) {
+  std::vector<int64_t> ids((size_t)std::max<int64_t>(A.getncol(), 1));
+  int64_t n = 0;
+  cbg_abort_on(cbg_grid_nonisolated(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), ids.data(), &n), "RemoveIsolated");
+  const std::vector<IT> nonisov(ids.begin(), ids.begin() + n);
+  A(nonisov, nonisov, true);
+  return nonisov;
+}
+// RandPermute (MCL.cpp:496-512), in place: A(p, p) with p = cbg_rand_perm(n, seed) (the reference
+// draws p with MTRand); returns p
+template <typename IT, typename NT, typename DER>
+std::vector<IT> RandPermute(SpParMat<IT, NT, DER>& A, uint64_t seed = 0x5EED) {
+  if (A.getnrow() != A.getncol()) cbg_abort_on(CBG_ERR_DIMMISMATCH, "RandPermute needs a square matrix");
+  std::vector<int64_t> p((size_t)std::max<int64_t>(A.getncol(), 1));
+  cbg_abort_on(cbg_rand_perm(A.getncol(), seed, p.data()), "RandPermute");
+  const std::vector<IT> pv(p.begin(), p.begin() + A.getncol());
+  A(pv, pv, true);
+  return pv;
+}
 // the reference's HipMCLParam fields this path reads (MCL.cpp:58-99), its defaults
 struct HipMCLParam {
   double inflation = 2.0, prunelimit = 1.0 / 10000.0, recover_pct = .9;
@@ -826,12 +882,18 @@ struct HipMCLParam {
   int phases = 1, perProcessMem = 0;
   bool preprune = false;       // forced; otherwise the reference's rule decides (MCL.cpp:531-538)
   int64_t max_iterations = 0;  // this library's extension: 0 = until chaos <= EPS
-  // filled by HipMCL: iterations run and the chaos of each
+  // MCL.cpp:517-521; off by default here (the reference's defaults: remove_isolated off, randpermute on)
+  bool remove_isolated = false, randpermute = false;
+  uint64_t perm_seed = 0x5EED;  // this library's RandPerm (cbg_rand_perm)
+  // filled by HipMCL: iterations run, the chaos of each, and the working matrix's dimension
   int iterations = 0;
   std::vector<double> chaos;
+  int64_t n_work = 0;
 };
-// HipMCL() (MCL.cpp:515-647), one layer, without RemoveIsolated / RandPermute: the
-// cluster of every vertex.  A is left unchanged (the reference iterates in place).
+// HipMCL() (MCL.cpp:515-647), one layer: the cluster of every vertex, in A's vertex numbering
+// also after RemoveIsolated / RandPermute (a removed vertex is a cluster of its own; the
+// reference leaves the reordered ids as a TODO, MCL.cpp:495).  A is left unchanged (the
+// reference iterates in place).
 template <typename IT, typename NT, typename DER>
 std::vector<IT> HipMCL(SpParMat<IT, NT, DER>& A, HipMCLParam& param) {
   cbg_hipmcl_params p{};
@@ -849,9 +911,17 @@ std::vector<IT> HipMCL(SpParMat<IT, NT, DER>& A, HipMCLParam& param) {
   };
   std::vector<int64_t> lab((size_t)std::max<int64_t>(A.getncol(), 1));
   int64_t its = 0;
-  cbg_abort_on(cbg_grid_hipmcl(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), &p, fn, &param.chaos, nullptr,
-                               lab.data(), nullptr, &its),
-               "HipMCL");
+  param.n_work = A.getncol();
+  if (param.remove_isolated || param.randpermute) {
+    const cbg_hipmcl_prep prep = {param.remove_isolated ? 1 : 0, param.randpermute ? 1 : 0, param.perm_seed};
+    cbg_abort_on(cbg_grid_hipmcl_prepared(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), &p, &prep, fn, &param.chaos,
+                                          nullptr, lab.data(), nullptr, &its, nullptr, &param.n_work),
+                 "HipMCL");
+  } else {
+    cbg_abort_on(cbg_grid_hipmcl(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), &p, fn, &param.chaos, nullptr,
+                                 lab.data(), nullptr, &its),
+                 "HipMCL");
+  }
   param.iterations = (int)its;
   return std::vector<IT>(lab.begin(), lab.begin() + A.getncol());
 }

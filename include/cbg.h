@@ -452,9 +452,9 @@ int cbg_grid_connected_components(cbg_grid* g, const cbg_tile* local, int64_t gn
  * pre-pruning (MCLPruneRecoverySelect), then while chaos > eps: A <- A * A with every
  * piece pruned (cbg_summa_spgemm_mcl), cbg_grid_inflate; finally the connected
  * components.  A stays on the device throughout.  RemoveIsolated and RandPermute
- * (MCL.cpp:477-512) need SpRef indexing and the 3D layers a third grid dimension: out of
- * scope.  The squaring multiplies A by a device copy of itself (one copy per
- * iteration): the public SUMMA's refusal of aliased operands stays. */
+ * (MCL.cpp:477-512) run before it in cbg_grid_hipmcl_prepared below; the 3D layers need a
+ * third grid dimension: out of scope.  The squaring multiplies A by a device copy of
+ * itself (one copy per iteration): the public SUMMA's refusal of aliased operands stays. */
 typedef struct cbg_hipmcl_params {
   double inflation;        /* > 0 */
   cbg_mcl_params prune;    /* hardThreshold, selectNum, recoverNum, recoverPct */
@@ -481,6 +481,85 @@ int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_
  * pruning inside them (device ms) and of the inflations */
 int cbg_last_hipmcl_stats(int64_t* iterations, double* chaos, int64_t* final_nnz, double* ms_expand,
                           double* ms_prune, double* ms_inflate);
+
+/* ---------------- sparse indexing (SpRef) ---------------- */
+/* SpDCCols::operator()(ri, ci) (SpDCCols.cpp:1355-1383) on one device tile:
+ * out is nri x nci, out(i, j) = t(ri[i], ci[j]); stored entries only, values copied bit for bit
+ * (explicit zeros, -0.0, NaN payloads kept), rows ascending in every column, empty columns not in jc.
+ * ri / ci: HOST int64 arrays; indices may repeat and may be left out.
+ * ri == NULL: all rows in order (nri ignored); ci == NULL likewise.
+ * (The reference spells "all" as an empty vector; here a non-NULL vector of length 0 gives an extent of 0.)
+ * An index outside the tile or a negative count: CBG_ERR_INVALIDPARAMS before any device work. */
+int cbg_tile_spref(const cbg_tile* t, const int64_t* ri, int64_t nri, const int64_t* ci, int64_t nci, cbg_tile* out);
+
+/* SpParMat::SubsRef_SR (SpParMat.cpp:2026-2247), collective over the grid, any pr x pc:
+ * the gm x gn distributed matrix whose tile is `local` -> this rank's tile of the nri x nci matrix
+ * B(i, j) = A(ri[i], ci[j]) in the standard block layout (SpParMat::Owner).
+ * ri / ci: HOST, GLOBAL indices, the same arrays on every rank (as `labels` of
+ * cbg_grid_connected_components); NULL = all.
+ * The reference multiplies by two boolean selection matrices (P * A * Q); here the entries
+ * are moved: the requested columns are gathered along the grid row first (whole columns, no
+ * sort), then the rows are relabelled along the grid column through the inverse of ri and
+ * every column is sorted by row -- not at all when ri is strictly increasing.
+ * An index below 0 or at or above its extent (the reference's own check, SpParMat.cpp:2051,
+ * lets the extent itself pass), a negative count, a NULL out, or gm / gn that do not fit the
+ * tile's place in the grid: CBG_ERR_INVALIDPARAMS on every rank before any device work.
+ * A new local block of 2^31 or more rows or columns: CBG_ERR_NOTSUPPORTED. */
+int cbg_grid_spref(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
+                   const int64_t* ci, int64_t nci, cbg_tile* out);
+
+/* p (HOST, n int64) = the stable argsort of key[i] = mix64(seed ^ (i * 0x9E3779B97F4A7C15)), i = 0..n-1
+ * (mix64: the finalizer of cbg_tile_digest).  Equal keys keep index order.  Computed on the host.
+ * This library's RandPerm (FullyDistVec::RandPerm as MCL.cpp:496-512 uses it): the
+ * reference's draws from MTRand and cannot be reproduced. */
+int cbg_rand_perm(int64_t n, uint64_t seed, int64_t* p);
+
+/* upper column length of each class of the indexing's column sort but the last (a wave's
+ * registers, a block's LDS; longer columns go through the radix sort): bounds[i] for
+ * i < min(n, 2); returns 2 */
+int cbg_spref_sort_bounds(int64_t* bounds, int n);
+/* the last indexing call's work on this rank (cbg_grid_hipmcl_prepared: summed over its
+ * two indexings): entries in / out, columns sorted by each class (columns of fewer than
+ * two entries are not counted), stored columns left unsorted because ri was strictly
+ * increasing, bytes of the remote tiles received.  counts[i] for i < min(n, CBG_SPREF_N);
+ * ms (may be NULL): CBG_SPREF_MS_N times in ms (column stage, row stage, sort): the sort's
+ * between device events, the stages' between stream-synchronized points (uploads of the index
+ * slices and waits for the broadcasts included).  Returns CBG_SPREF_N. */
+enum {
+  CBG_SPREF_ENTRIES_IN = 0,
+  CBG_SPREF_ENTRIES_OUT = 1,
+  CBG_SPREF_SORT_CLASS0 = 2, /* + c: wave, LDS, radix */
+  CBG_SPREF_COLS_MONOTONE = 5,
+  CBG_SPREF_BYTES_RECV = 6,
+  CBG_SPREF_N = 7
+};
+enum { CBG_SPREF_MS_COL = 0, CBG_SPREF_MS_ROW = 1, CBG_SPREF_MS_SORT = 2, CBG_SPREF_MS_N = 3 };
+int cbg_last_spref_stats(int64_t* counts, int n, double* ms);
+
+/* nonisov of RemoveIsolated (MCL.cpp:476-486), collective over the grid: the vertices of the
+ * gn x gn distributed matrix whose column sum (cbg_grid_reduce_cols(CBG_RED_SUM, 0.0): the same
+ * bits on every rank of a grid column) is > 0, ascending; each rank's slice allgathered along
+ * its grid row.  ids: HOST, gn int64; *n their number.  The same list on every rank. */
+int cbg_grid_nonisolated(cbg_grid* g, const cbg_tile* local, int64_t gn, int64_t* ids, int64_t* n);
+
+typedef struct cbg_hipmcl_prep {
+  int32_t remove_isolated, randpermute;
+  uint64_t perm_seed;
+} cbg_hipmcl_prep;
+/* cbg_grid_hipmcl preceded by RemoveIsolated (MCL.cpp:476-493: A(nonisov, nonisov) with nonisov
+ * the vertices whose column sum is > 0) and / or RandPermute (MCL.cpp:496-512: A(p, p) with
+ * p = cbg_rand_perm(n_work, perm_seed)), in that order (MCL.cpp:517-521).
+ * prep == NULL or both flags 0: exactly cbg_grid_hipmcl.
+ * labels (HOST, gn): in the ORIGINAL vertex numbering, canonical as before (components ordered by their
+ *   smallest original vertex); every removed vertex is a cluster of its own.
+ *   (The reference leaves "handle reordered cluster ids" as a TODO, MCL.cpp:495; this library maps back.)
+ * work_ids (HOST, gn, may be NULL): work_ids[k] = the original vertex of working vertex k, k < *n_work.
+ * n_work (may be NULL): the working matrix's dimension.
+ * final_local: the converged matrix in the working numbering (n_work x n_work). */
+int cbg_grid_hipmcl_prepared(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_hipmcl_params* params,
+                             const cbg_hipmcl_prep* prep, cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local,
+                             int64_t* labels, int64_t* nclusters, int64_t* iterations, int64_t* work_ids,
+                             int64_t* n_work);
 
 /* SpParMat::Transpose (SpParMat.cpp:3528-3590), collective over a square grid:
  * out = this rank's tile of the transposed matrix (the transpose of the
