@@ -25,7 +25,6 @@ int summa_spgemm_phased(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64
                         int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C);
 int grid_transpose(cbg_grid* g, const cbg_tile& T, cbg_tile& out);
 int agree(cbg_grid* g, int rc);
-std::string& step_error();
 int grid_block_extract(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, int dim, int64_t lo, int64_t hi,
                        cbg_tile& out);
 int grid_mcl_prune(cbg_grid* g, const cbg_tile& T, const cbg_mcl_params* p, cbg_tile& out);

@@ -30,6 +30,37 @@ struct HipError : std::runtime_error {
                             CBG_ERR_HIP);                                                           \
   } while (0)
 
+typedef unsigned long long u64;
+
+// code of a failure inside a collective step (the step's exception is not
+// rethrown: the caller must still reach the next agreement); the first message
+// of the calling thread is kept for cbg_last_error() (cbg_summa.cpp)
+std::string& step_error();
+template <class F>
+int step(F&& f) {
+  try {
+    f();
+    return CBG_OK;
+  } catch (const HipError& e) {
+    if (std::getenv("CBG_DEBUG_ERRORS")) std::fprintf(stderr, "[cbg] %s\n", e.what());
+    if (step_error().empty()) step_error() = e.what();
+    return e.code;
+  } catch (const std::bad_alloc&) {
+    if (step_error().empty()) step_error() = "host allocation failed";
+    return CBG_ERR_OOM;
+  } catch (const std::exception& e) {  // anything else still reaches the next agreement
+    if (step_error().empty()) step_error() = e.what();
+    return CBG_ERR_HIP;
+  }
+}
+
+// mask of the bits of values in [0, maxval] (the digits a radix sort has to visit)
+inline u64 low_bits(int64_t maxval) {
+  u64 m = 0;
+  while ((u64)(maxval > 0 ? maxval : 0) > m) m = (m << 1) | 1ull;
+  return m;
+}
+
 // Caching device allocator: blocks are rounded up (>= 2 MiB granules for big
 // requests) and recycled by size so that repeated multiplies never touch
 // hipMalloc/hipFree in steady state (cdna_hip_programming.md Guideline 9).
@@ -293,6 +324,9 @@ bool tile_equal(const cbg_tile& a, const cbg_tile& b, double eps, hipStream_t s)
 // phase planning: dim 0 = nonzeros per column (length n), 1 = per row (length m),
 // into the device array d zero-padded to `padded` entries (stream synchronized)
 void tile_counts_device(const cbg_tile& t, int dim, int32_t* d, int64_t padded, hipStream_t s);
+// dense column map (max(n, 1) entries each, queued on s): pos[j] = position of column j in
+// jc, -1 where it stores nothing; len (may be NULL) = its length, 0 there
+void tile_col_map(const cbg_tile& t, int32_t* pos, int64_t* len, hipStream_t s);
 // sum over B's entries (k, j) of a[k] (device array of B.m values): A*B's flops for A's column counts
 int64_t entry_sum_device(const cbg_tile& B, const int32_t* a, hipStream_t s);
 // sum_k a[k] * b[k] over k < K with a, b stored as blocks (see cbg_tile.hip)

@@ -17,21 +17,15 @@
 #include <cfloat>
 #include <cmath>
 
-#include "cbg_device.h"
-#include "cbg_internal.h"
+#include "cbg_rebuild.h"
 
 #pragma clang fp contract(off)
 
 namespace cbg {
-std::string& step_error();
 
 namespace {
 constexpr int MOM_GROUP_MAX = 16;
 constexpr int MOM_WAVE_MAX = 4096;
-
-typedef unsigned long long u64;
-
-inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
 
 // what a pass over a column does with its values
 enum {
@@ -239,23 +233,6 @@ void moments_launch(const cbg_tile& t, const double* inv, double power, double* 
   CBG_HIP(hipGetLastError());
 }
 
-template <class F>
-int try_step(F&& f) {
-  try {
-    f();
-    return CBG_OK;
-  } catch (const HipError& e) {
-    if (step_error().empty()) step_error() = e.what();
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    if (step_error().empty()) step_error() = "host allocation failed";
-    return CBG_ERR_OOM;
-  } catch (const std::exception& e) {
-    if (step_error().empty()) step_error() = e.what();
-    return CBG_ERR_HIP;
-  }
-}
-
 // One pass over the tile and the combine along the grid column: mom (4n device doubles)
 // ends as the moments of the whole columns, the same bits on every rank of the column.
 // pend: this rank's failure so far (reported at the agreement).
@@ -263,7 +240,7 @@ template <int PASS>
 int col_pass(const ColComm& cc, const cbg_tile& T, const double* inv, double power, double* mom, hipStream_t s,
              int pend) {
   const int64_t n = std::max<int64_t>(T.n, 1);
-  if (!pend) pend = try_step([&] {
+  if (!pend) pend = step([&] {
     hipLaunchKernelGGL(k_mom_preset, dim3(nblk(4 * n, 256)), dim3(256), 0, s, mom, n);
     // the arrays are laid out for T.n columns: n == T.n but for an empty tile, whose kernels do not run
     moments_launch<PASS>(T, inv, power, mom, s);
@@ -272,9 +249,9 @@ int col_pass(const ColComm& cc, const cbg_tile& T, const double* inv, double pow
   if (cc.P == 1) return pend;
   // every rank holds its receive buffer before anyone posts the gather
   DBuf<double> all;
-  if (!pend) pend = try_step([&] { all.reset((size_t)4 * n * cc.P); });
+  if (!pend) pend = step([&] { all.reset((size_t)4 * n * cc.P); });
   if (int rc = cc.agree_vals(pend, nullptr, 0, nullptr)) return rc;
-  const int rc = try_step([&] {
+  const int rc = step([&] {
     cc.allgather_dev(mom, all.p, sizeof(double) * 4 * n);
     hipLaunchKernelGGL(k_mom_combine, dim3(nblk(n, 256)), dim3(256), 0, s, all.p, cc.P, n, mom);
     CBG_HIP(hipGetLastError());
@@ -325,13 +302,13 @@ int grid_reduce_cols_device(const ColComm& cc, const cbg_tile& T, int what, doub
                             hipStream_t s) {
   const int64_t n = std::max<int64_t>(T.n, 1);
   DBuf<double> mom, out;
-  int pend = try_step([&] {
+  int pend = step([&] {
     mom.reset(4 * n);
     out.reset(n);
   });
   // a reduce pass leaves val as it is
   int rc = col_pass<PASS_REDUCE>(cc, T, nullptr, 1.0, mom.p, s, pend);
-  if (!rc) rc = try_step([&] {
+  if (!rc) rc = step([&] {
     hipLaunchKernelGGL(k_mom_pick, dim3(nblk(n, 256)), dim3(256), 0, s, mom.p, n, what, identity, out.p);
     CBG_HIP(hipGetLastError());
     if (T.n > 0) CBG_HIP(hipMemcpyAsync(out_host, out.p, sizeof(double) * T.n, hipMemcpyDeviceToHost, s));
@@ -343,12 +320,12 @@ int grid_reduce_cols_device(const ColComm& cc, const cbg_tile& T, int what, doub
 int grid_make_col_stochastic_device(const ColComm& cc, cbg_tile& T, hipStream_t s) {
   const int64_t n = std::max<int64_t>(T.n, 1);
   DBuf<double> mom, inv;
-  int pend = try_step([&] {
+  int pend = step([&] {
     mom.reset(4 * n);
     inv.reset(n);
   });
   int rc = col_pass<PASS_REDUCE>(cc, T, nullptr, 1.0, mom.p, s, pend);
-  if (!rc) rc = try_step([&] {
+  if (!rc) rc = step([&] {
     hipLaunchKernelGGL(k_safe_inv, dim3(nblk(n, 256)), dim3(256), 0, s, mom.p, n, inv.p);
     scale_launch(T, inv.p, s);
     CBG_HIP(hipStreamSynchronize(s));
@@ -360,9 +337,9 @@ int grid_make_col_stochastic_device(const ColComm& cc, cbg_tile& T, hipStream_t 
 int grid_chaos_device(const ColComm& cc, const cbg_tile& T, double* chaos, hipStream_t s) {
   const int64_t n = std::max<int64_t>(T.n, 1);
   DBuf<double> mom;
-  int pend = try_step([&] { mom.reset(4 * n); });
+  int pend = step([&] { mom.reset(4 * n); });
   int rc = col_pass<PASS_REDUCE>(cc, T, nullptr, 1.0, mom.p, s, pend);
-  if (!rc) rc = try_step([&] { *chaos = chaos_of(mom.p, n, s); });
+  if (!rc) rc = step([&] { *chaos = chaos_of(mom.p, n, s); });
   return cc.agree_vals(rc, nullptr, 0, nullptr);
 }
 
@@ -374,20 +351,20 @@ int grid_inflate_device(const ColComm& cc, cbg_tile& T, double power, double* ch
   auto mark = [&](int i) {
     if (ms) CBG_HIP(hipEventRecord(ev[i], s));
   };
-  int pend = try_step([&] {
+  int pend = step([&] {
     mom.reset(4 * n);
     inv.reset(n);
     for (int i = 0; ms && i < 6; ++i) CBG_HIP(hipEventCreate(&ev[i]));
     mark(0);
   });
   int rc = col_pass<PASS_REDUCE>(cc, T, nullptr, 1.0, mom.p, s, pend);  // 1: column sums
-  if (!rc) pend = try_step([&] {
+  if (!rc) pend = step([&] {
     mark(1);
     hipLaunchKernelGGL(k_safe_inv, dim3(nblk(n, 256)), dim3(256), 0, s, mom.p, n, inv.p);
     mark(2);
   });
   if (!rc) rc = col_pass<PASS_INFLATE>(cc, T, inv.p, power, mom.p, s, pend);  // 2: scale, chaos moments, pow, sums
-  if (!rc) rc = try_step([&] {
+  if (!rc) rc = step([&] {
     mark(3);
     *chaos = chaos_of(mom.p, n, s);
     hipLaunchKernelGGL(k_safe_inv, dim3(nblk(n, 256)), dim3(256), 0, s, mom.p, n, inv.p);
@@ -410,24 +387,19 @@ int grid_inflate_device(const ColComm& cc, cbg_tile& T, double power, double* ch
 // Loops on the diagonal (SpParMat.cpp:3257-3335).  Local column j of the tile is
 // global column coff + j; its diagonal entry is local row coff + j - roff, inside
 // the tile when that is in [0, m).
-//   k_loop_count: per dense column its new length, whether it stays nonempty,
-//                 where the diagonal row sorts into it and whether it is there;
-//   two scans; k_loop_scatter: one wave per column copies it, shifted by the
-//   removed or inserted entry (rows stay ascending).
+//   k_loop_count: per dense column its new length, where the diagonal row sorts
+//                 into it and whether it is there;
+//   EmitLoops:    a wave copies the column, shifted by the removed or inserted
+//                 entry (rows stay ascending).
 // ---------------------------------------------------------------------------
 namespace {
 enum { LOOP_REMOVE = 0, LOOP_ADD = 1 };
 enum { DIAG_HERE = 1, DIAG_STORED = 2 };
 
-__global__ void k_col_pos32(const int32_t* jc, int64_t nzc, int32_t* pos) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < nzc) pos[jc[p]] = (int32_t)p;
-}
-
 __global__ void k_loop_count(const int64_t* __restrict__ cp, const int32_t* __restrict__ ir,
                              const int32_t* __restrict__ pos, int64_t m, int64_t n, int64_t diag_off, int mode,
-                             int64_t* __restrict__ nlen, int32_t* __restrict__ ne, int32_t* __restrict__ code,
-                             int32_t* __restrict__ at, u64* __restrict__ nfound) {
+                             int64_t* __restrict__ nlen, int32_t* __restrict__ code, int32_t* __restrict__ at,
+                             u64* __restrict__ nfound) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int32_t p = pos[j];
@@ -448,49 +420,42 @@ __global__ void k_loop_count(const int64_t* __restrict__ cp, const int32_t* __re
   }
   if (c & DIAG_STORED) atomicAdd(nfound, 1ull);
   nlen[j] = len;
-  ne[j] = len > 0 ? 1 : 0;
   code[j] = c;
   at[j] = (int32_t)k;
 }
 
-__global__ __launch_bounds__(256) void k_loop_scatter(const int64_t* __restrict__ cp, const int32_t* __restrict__ ir,
-                                                      const double* __restrict__ val, const int32_t* __restrict__ pos,
-                                                      int64_t n, int64_t diag_off, int mode, int replace, int fix_min,
-                                                      const double* __restrict__ loopval,
-                                                      const int64_t* __restrict__ ncp, const int64_t* __restrict__ npos,
-                                                      const int32_t* __restrict__ code, const int32_t* __restrict__ at,
-                                                      int64_t* __restrict__ ocp, int32_t* __restrict__ ojc,
-                                                      int32_t* __restrict__ oir, double* __restrict__ oval) {
-  const int lane = threadIdx.x & 63;
-  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (j >= n) return;
-  if (j == n - 1 && lane == 0) ocp[npos[n]] = ncp[n];
-  const int64_t o = ncp[j];
-  if (ncp[j + 1] == o) return;
-  if (lane == 0) {
-    ojc[npos[j]] = (int32_t)j;
-    ocp[npos[j]] = o;
+struct EmitLoops {
+  const int64_t* cp;
+  const int32_t* ir;
+  const double* val;
+  const int32_t* pos;
+  int64_t diag_off;
+  int mode, replace, fix_min;
+  const double* loopval;
+  const int32_t *code, *at;
+  __device__ __forceinline__ void operator()(int64_t j, int64_t o, int32_t* oir, double* oval) const {
+    const int lane = lane_id();
+    const int32_t p = pos[j];
+    const int64_t b = p < 0 ? 0 : cp[p], len = p < 0 ? 0 : cp[p + 1] - b;
+    const int c = code[j];
+    const int64_t k = at[j];
+    const bool here = c & DIAG_HERE, stored = c & DIAG_STORED;
+    const bool drop = mode == LOOP_REMOVE && stored, insert = mode == LOOP_ADD && here && !stored;
+    for (int64_t i = lane; i < len; i += WAVE) {
+      if (drop && i == k) continue;
+      double v = val[b + i];
+      if (fix_min && v == DBL_MIN) v = 1.0;  // AdjustLoops' Apply (MCL.cpp:469)
+      if (mode == LOOP_ADD && stored && replace && i == k) v = loopval[j];
+      const int64_t d = o + i - (drop && i > k ? 1 : 0) + (insert && i >= k ? 1 : 0);
+      oir[d] = ir[b + i];
+      oval[d] = v;
+    }
+    if (insert && lane == 0) {
+      oir[o + k] = (int32_t)(j + diag_off);
+      oval[o + k] = loopval[j];
+    }
   }
-  const int32_t p = pos[j];
-  const int64_t b = p < 0 ? 0 : cp[p], len = p < 0 ? 0 : cp[p + 1] - b;
-  const int c = code[j];
-  const int64_t k = at[j];
-  const bool here = c & DIAG_HERE, stored = c & DIAG_STORED;
-  const bool drop = mode == LOOP_REMOVE && stored, insert = mode == LOOP_ADD && here && !stored;
-  for (int64_t i = lane; i < len; i += WAVE) {
-    if (drop && i == k) continue;
-    double v = val[b + i];
-    if (fix_min && v == DBL_MIN) v = 1.0;  // AdjustLoops' Apply (MCL.cpp:469)
-    if (mode == LOOP_ADD && stored && replace && i == k) v = loopval[j];
-    const int64_t d = o + i - (drop && i > k ? 1 : 0) + (insert && i >= k ? 1 : 0);
-    oir[d] = ir[b + i];
-    oval[d] = v;
-  }
-  if (insert && lane == 0) {
-    oir[o + k] = (int32_t)(j + diag_off);
-    oval[o + k] = loopval[j];
-  }
-}
+};
 }  // namespace
 
 // mode LOOP_REMOVE / LOOP_ADD on one tile; loopval: device, n entries (ADD); found: the
@@ -503,34 +468,18 @@ void tile_edit_loops_device(const cbg_tile& T, int64_t diag_off, int mode, int r
     if (found) *found = 0;
     return;
   }
-  DeferredFree df;
-  DBuf<int64_t> nlen(n + 1), ncp(n + 1), npos(n + 1);
-  DBuf<int32_t> pos(n), ne(n), code(n), at(n);
+  DBuf<int64_t> nlen(n + 1);
+  DBuf<int32_t> pos(n), code(n), at(n);
   DBuf<u64> nf(1);
-  CBG_HIP(hipMemsetAsync(pos.p, 0xff, sizeof(int32_t) * n, s));
   CBG_HIP(hipMemsetAsync(nf.p, 0, sizeof(u64), s));
-  if (T.nzc > 0) hipLaunchKernelGGL(k_col_pos32, dim3(nblk(T.nzc, 256)), dim3(256), 0, s, T.jc, T.nzc, pos.p);
+  tile_col_map(T, pos.p, nullptr, s);
   hipLaunchKernelGGL(k_loop_count, dim3(nblk(n, 256)), dim3(256), 0, s, T.cp, T.ir, pos.p, T.m, n, diag_off, mode, nlen.p,
-                     ne.p, code.p, at.p, nf.p);
-  exclusive_scan_i64(nlen.p, ncp.p, n, s, &df);
-  exclusive_scan_i32_to_i64(ne.p, npos.p, n, s, &df);
-  int64_t tot[2] = {0, 0};
-  u64 nfound = 0;
-  CBG_HIP(hipMemcpyAsync(&tot[0], ncp.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&tot[1], npos.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&nfound, nf.p, sizeof(u64), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  df.synced = true;
-  TileGuard o;
-  tile_alloc_device(o.t, T.m, T.n, tot[0], tot[1]);
-  if (tot[0] > 0) {
-    hipLaunchKernelGGL(k_loop_scatter, dim3(nblk(n, 4)), dim3(256), 0, s, T.cp, T.ir, T.val, pos.p, n, diag_off, mode,
-                       replace, fix_min, loopval, ncp.p, npos.p, code.p, at.p, o.t.cp, o.t.jc, o.t.ir, o.t.val);
-    CBG_HIP(hipGetLastError());
-    CBG_HIP(hipStreamSynchronize(s));  // the temporaries go back to the pool on return
-  }
-  if (found) *found = (int64_t)nfound;
-  out = o.release();
+                     code.p, at.p, nf.p);
+  int64_t nfound = 0;  // read back with the totals
+  tile_from_columns(T.m, T.n, n, nullptr, nlen.p,
+                    EmitLoops{T.cp, T.ir, T.val, pos.p, diag_off, mode, replace, fix_min, loopval, code.p, at.p}, out, s,
+                    reinterpret_cast<const int64_t*>(nf.p), &nfound);
+  if (found) *found = nfound;
 }
 
 // ---------------------------------------------------------------------------

@@ -71,12 +71,6 @@ static void keys_to_tile(unsigned long long* keys, double* vals, int64_t n, int6
   CBG_HIP(hipStreamSynchronize(s));
 }
 
-static unsigned long long low_bits(int64_t maxval) {  // mask of the bits of values in [0, maxval]
-  unsigned long long m = 0;
-  while ((unsigned long long)maxval > m) m = (m << 1) | 1ull;
-  return m;
-}
-
 void tile_transpose(const cbg_tile& T, cbg_tile& out, hipStream_t s) {
   out = cbg_tile{};
   out.on_device = 1;

@@ -10,13 +10,11 @@
 #include <cstring>
 #include <tuple>
 
-#include "cbg_internal.h"
+#include "cbg_rebuild.h"
 
 namespace cbg {
-std::string& step_error();
 
 namespace {
-constexpr int WAVE = 64;
 // k-select length classes (cbg_mcl_kselect_bounds): a wave's registers (8 keys
 // per lane), a block's LDS at 32 KiB and at 128 KiB of keys, longer: streamed
 constexpr int KSEL_WAVE_MAX = 512;
@@ -27,8 +25,6 @@ constexpr int KSEL_STREAM_CHUNK = 4096;  // ... in chunks of this many entries
 // column statistics: 16 lanes per column up to 16 entries, a wave up to 4096, a block above
 constexpr int STAT_GROUP_MAX = 16;
 constexpr int STAT_WAVE_MAX = 4096;
-
-typedef unsigned long long u64;
 
 // order-preserving key: a < b  <=>  key(a) < key(b); -0.0 and +0.0 share a key
 __device__ inline u64 key_of(double v) {
@@ -45,15 +41,6 @@ __device__ inline double val_of(u64 k) {
 __global__ void k_fill_f64(double* p, int64_t n, double v) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
-}
-
-// pos[j] = position of column j in jc (-1 preset), all[j] = its length (0 preset)
-__global__ void k_col_pos(const int64_t* cp, const int32_t* jc, int64_t nzc, int32_t* pos, int64_t* all) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= nzc) return;
-  const int32_t j = jc[p];
-  pos[j] = (int32_t)p;
-  if (all) all[j] = cp[p + 1] - cp[p];
 }
 
 // ---------------------------------------------------------------------------
@@ -427,72 +414,23 @@ __global__ __launch_bounds__(256) void k_union_gather(const int64_t* SZ, const i
 }
 
 // ---------------------------------------------------------------------------
-// compaction: k_prune_count is k_col_stats without the sums (kept entries per
-// nonempty column, non-strict); after the scans one wave per surviving column
-// copies its kept entries in order (ballot ranks), values untouched
+// compaction: the count is k_col_stats without the sums (kept entries per stored
+// column, non-strict); the emit copies a surviving column's kept entries in
+// order, values untouched
 // ---------------------------------------------------------------------------
-__global__ void k_nonempty(const int64_t* kept, int64_t nzc, int32_t* ne) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < nzc) ne[p] = kept[p] > 0 ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_prune_scatter(const int64_t* __restrict__ cp, const int32_t* __restrict__ jc,
-                                                       const int32_t* __restrict__ ir, const double* __restrict__ val,
-                                                       int64_t nzc, const double* __restrict__ thr,
-                                                       const int64_t* __restrict__ kept, const int64_t* __restrict__ ncp,
-                                                       const int64_t* __restrict__ npos, int64_t* __restrict__ ocp,
-                                                       int32_t* __restrict__ ojc, int32_t* __restrict__ oir,
-                                                       double* __restrict__ oval) {
-  const int lane = threadIdx.x & 63;
-  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= nzc) return;
-  if (p == nzc - 1 && lane == 0) ocp[npos[nzc]] = ncp[nzc];
-  if (kept[p] <= 0) return;
-  const int64_t b = cp[p], len = cp[p + 1] - b;
-  const int32_t j = jc[p];
-  const double t = thr[j];
-  int64_t o = ncp[p];
-  if (lane == 0) {
-    ojc[npos[p]] = j;
-    ocp[npos[p]] = o;
+struct EmitKept {
+  const int64_t* cp;
+  const int32_t *jc, *ir;
+  const double *val, *thr;
+  struct Keep {
+    static constexpr bool by_row = false;
+    double t;
+    __device__ __forceinline__ bool operator()(int32_t, double v) const { return !(v < t); }
+  };
+  __device__ __forceinline__ void operator()(int64_t p, int64_t dst, int32_t* oir, double* oval) const {
+    copy_filtered(ir, val, cp[p], cp[p + 1] - cp[p], Keep{thr[jc[p]]}, RowSame(), oir, oval, dst);
   }
-  for (int64_t x0 = 0; x0 < len; x0 += WAVE) {
-    const int64_t x = x0 + lane;
-    double v = 0.0;
-    int32_t r = 0;
-    bool keep = false;
-    if (x < len) {
-      v = val[b + x];
-      r = ir[b + x];
-      keep = !(v < t);
-    }
-    const u64 m = __ballot(keep);
-    if (keep) {
-      const int64_t d = o + __popcll(m & ((1ull << lane) - 1));
-      oir[d] = r;
-      oval[d] = v;
-    }
-    o += __popcll(m);
-  }
-}
-
-inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
-template <class F>
-int try_step(F&& f) {
-  try {
-    f();
-    return CBG_OK;
-  } catch (const HipError& e) {
-    if (step_error().empty()) step_error() = e.what();
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    if (step_error().empty()) step_error() = "host allocation failed";
-    return CBG_ERR_OOM;
-  } catch (const std::exception& e) {
-    if (step_error().empty()) step_error() = e.what();
-    return CBG_ERR_HIP;
-  }
-}
+};
 
 // device time of the prune's stages (events read after the call's last sync)
 struct StageClock {
@@ -524,12 +462,6 @@ struct StageClock {
     }
   }
 };
-
-template <class K>
-void set_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    CBG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
 
 // st: 5 zeroed device counters (see above), read into sth after the wave kernel (one
 // stream synchronization: the other classes are launched on their exact counts);
@@ -619,27 +551,9 @@ void tile_prune_column_device(const cbg_tile& t, const double* thr, cbg_tile& ou
     tile_alloc_device(out, t.m, t.n, 0, 0);
     return;
   }
-  DeferredFree df;
-  DBuf<int64_t> kept(t.nzc + 1), ncp(t.nzc + 1), npos(t.nzc + 1);
-  DBuf<int32_t> ne(t.nzc);
-  col_stats_launch<false>(t, thr, 0, 0, kept.p, nullptr, s);  // k_prune_count
-  hipLaunchKernelGGL(k_nonempty, dim3(nblk(t.nzc, 256)), dim3(256), 0, s, kept.p, t.nzc, ne.p);
-  exclusive_scan_i64(kept.p, ncp.p, t.nzc, s, &df);
-  exclusive_scan_i32_to_i64(ne.p, npos.p, t.nzc, s, &df);
-  int64_t tot[2] = {0, 0};
-  CBG_HIP(hipMemcpyAsync(&tot[0], ncp.p + t.nzc, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&tot[1], npos.p + t.nzc, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  df.synced = true;
-  TileGuard o;
-  tile_alloc_device(o.t, t.m, t.n, tot[0], tot[1]);
-  if (tot[0] > 0) {
-    hipLaunchKernelGGL(k_prune_scatter, dim3(nblk(t.nzc, 4)), dim3(256), 0, s, t.cp, t.jc, t.ir, t.val, t.nzc, thr,
-                       kept.p, ncp.p, npos.p, o.t.cp, o.t.jc, o.t.ir, o.t.val);
-    CBG_HIP(hipGetLastError());
-    CBG_HIP(hipStreamSynchronize(s));  // the temporaries go back to the pool on return
-  }
-  out = o.release();
+  DBuf<int64_t> kept(t.nzc + 1);
+  col_stats_launch<false>(t, thr, 0, 0, kept.p, nullptr, s);
+  tile_from_columns(t.m, t.n, t.nzc, t.jc, kept.p, EmitKept{t.cp, t.jc, t.ir, t.val, thr}, out, s);
 }
 
 namespace {
@@ -656,7 +570,7 @@ int col_kselect(const ColComm& cc, const cbg_tile& T, const int32_t* pos, const 
   u64 sth[5] = {};
   int64_t total = 0;
   const int64_t L1 = std::max<int64_t>(L, 1);
-  int rc = try_step([&] {
+  int rc = step([&] {
     beg.reset(L1);
     end.reset(L1);
     st.reset(5);
@@ -689,7 +603,7 @@ int col_kselect(const ColComm& cc, const cbg_tile& T, const int32_t* pos, const 
   DBuf<double> ALL, u;
   int64_t utotal = 0;
   for (auto t : tots) utotal += t;
-  rc = try_step([&] {
+  rc = step([&] {
     obuf.reset(stride);
     SZ.reset((size_t)cc.P * L1);
     roff.reset((size_t)cc.P * (L1 + 1));
@@ -705,7 +619,7 @@ int col_kselect(const ColComm& cc, const cbg_tile& T, const int32_t* pos, const 
     CBG_HIP(hipStreamSynchronize(s));
   });
   if ((rc = cc.agree_vals(rc, nullptr, 0, nullptr))) return rc;
-  return try_step([&] {
+  return step([&] {
     DeferredFree df2;
     cc.allgather_dev(sz.p, SZ.p, sizeof(int64_t) * L1);
     cc.allgather_dev(obuf.p, ALL.p, sizeof(double) * stride);
@@ -747,14 +661,11 @@ int grid_kselect_cols(const ColComm& cc, const cbg_tile& T, const int32_t* cols_
     bad = cols_host[i] < 0 || cols_host[i] >= T.n || seen[cols_host[i]];
     if (!bad) seen[cols_host[i]] = 1;
   }
-  int rc = bad ? (int)CBG_ERR_INVALIDPARAMS : try_step([&] {
+  int rc = bad ? (int)CBG_ERR_INVALIDPARAMS : step([&] {
     pos.reset(std::max<int64_t>(T.n, 1));
     list.reset(std::max<int64_t>(ncols, 1));
     out.reset(std::max<int64_t>(ncols, 1));
-    CBG_HIP(hipMemsetAsync(pos.p, 0xff, sizeof(int32_t) * std::max<int64_t>(T.n, 1), s));
-    if (T.nzc)
-      hipLaunchKernelGGL(k_col_pos, dim3(nblk(T.nzc, 256)), dim3(256), 0, s, T.cp, T.jc, T.nzc, pos.p,
-                         (int64_t*)nullptr);
+    tile_col_map(T, pos.p, nullptr, s);
     if (ncols) CBG_HIP(hipMemcpyAsync(list.p, cols_host, sizeof(int32_t) * ncols, hipMemcpyHostToDevice, s));
     CBG_HIP(hipStreamSynchronize(s));
   });
@@ -768,7 +679,7 @@ int grid_kselect_cols(const ColComm& cc, const cbg_tile& T, const int32_t* cols_
   if (ncols == 0 && cc.P == 1) return CBG_OK;
   rc = col_kselect(cc, T, pos.p, list.p, ncols, k, out.p, s);
   if (!rc && ncols)
-    rc = try_step([&] { CBG_HIP(hipMemcpy(kth_host, out.p, sizeof(double) * ncols, hipMemcpyDeviceToHost)); });
+    rc = step([&] { CBG_HIP(hipMemcpy(kth_host, out.p, sizeof(double) * ncols, hipMemcpyDeviceToHost)); });
   return cc.agree_vals(rc, nullptr, 0, nullptr);
 }
 
@@ -798,7 +709,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
   };
   // statistics of the whole grid column (summed in rank order); pend: this rank's failure so far
   auto stats = [&](int pend, int strict, int64_t* cnt, double* sum) {
-    if (!pend) pend = try_step([&] {
+    if (!pend) pend = step([&] {
       clock.begin(CBG_MCL_MS_STATS);
       tile_col_stats_device(T, thr.p, strict, cnt, sum, s);
       if (cc.P > 1) {
@@ -811,7 +722,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
     });
     if (cc.P == 1) return pend;
     if (int rc = agree(pend, nullptr)) return rc;
-    return try_step([&] {
+    return step([&] {
       cc.allgather_dev(pack.p, packs.p, (size_t)24 * n);
       hipLaunchKernelGGL(k_stats_combine, dim3(nblk(n, 256)), dim3(256), 0, s, packs.p, cc.P, n, cnt, sum,
                          strict ? all.p : off.p);  // `all` is combined once (off: scratch)
@@ -821,7 +732,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
   auto select_into_thr = [&](int64_t L, int64_t k) {
     clock.begin(CBG_MCL_MS_KSELECT);
     int rc = col_kselect(cc, T, pos.p, list.p, L, k, kth.p, s);
-    if (!rc) rc = try_step([&] {
+    if (!rc) rc = step([&] {
       if (L > 0) hipLaunchKernelGGL(k_scatter_thr, dim3(nblk(L, 256)), dim3(256), 0, s, list.p, kth.p, L, thr.p);
       CBG_HIP(hipGetLastError());
       clock.end();
@@ -829,22 +740,19 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
     return rc;
   };
 
-  int pend = pend0 ? pend0 : try_step([&] {
+  int pend = pend0 ? pend0 : step([&] {
     thr.reset(n), sum0.reset(n), sum1.reset(n), kth.reset(n);
     cnt0.reset(n), cnt1.reset(n), all.reset(n), off.reset(n + 1);
     pos.reset(n), inR.reset(n), inS.reset(n), f2.reset(n), list.reset(n);
     if (cc.P > 1) pack.reset(3 * n), packs.reset((size_t)3 * n * cc.P);
     hipLaunchKernelGGL(k_fill_f64, dim3(nblk(n, 256)), dim3(256), 0, s, thr.p, n, h);
-    CBG_HIP(hipMemsetAsync(pos.p, 0xff, sizeof(int32_t) * n, s));
-    CBG_HIP(hipMemsetAsync(all.p, 0, sizeof(int64_t) * n, s));
-    if (T.nzc)
-      hipLaunchKernelGGL(k_col_pos, dim3(nblk(T.nzc, 256)), dim3(256), 0, s, T.cp, T.jc, T.nzc, pos.p, all.p);
+    tile_col_map(T, pos.p, all.p, s);
   });
   pend = stats(pend, 1, cnt0.p, sum0.p);
   int rc = 0;
   int64_t nR = 0, nS = 0, n2 = 0;
   if (R > 0) {  // recovery
-    if (!pend) pend = try_step([&] {
+    if (!pend) pend = step([&] {
       hipLaunchKernelGGL(k_flag_recover, dim3(nblk(n, 256)), dim3(256), 0, s, cnt0.p, sum0.p, all.p, T.n, R, q, inR.p);
       nR = build_list(inR.p, T.n, off.p, list.p, s);
     });
@@ -852,7 +760,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
     if (nR > 0 || cc.P > 1) pend = select_into_thr(nR, R);
   }
   if (S > 0) {  // selection, then recovery of what selection cut too far
-    if (!pend) pend = try_step([&] {
+    if (!pend) pend = step([&] {
       hipLaunchKernelGGL(k_flag_select, dim3(nblk(n, 256)), dim3(256), 0, s, cnt0.p, R > 0 ? inR.p : (int32_t*)nullptr,
                          T.n, S, inS.p);
       nS = build_list(inS.p, T.n, off.p, list.p, s);
@@ -862,7 +770,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
       pend = select_into_thr(nS, S);
       if (R > 0) {
         pend = stats(pend, 0, cnt1.p, sum1.p);
-        if (!pend) pend = try_step([&] {
+        if (!pend) pend = step([&] {
           hipLaunchKernelGGL(k_flag_recover2, dim3(nblk(n, 256)), dim3(256), 0, s, cnt1.p, sum1.p, inS.p, T.n, R, q,
                              f2.p);
           n2 = build_list(f2.p, T.n, off.p, list.p, s);
@@ -873,7 +781,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
     }
   }
   TileGuard o;
-  if (!pend) pend = try_step([&] {
+  if (!pend) pend = step([&] {
     clock.begin(CBG_MCL_MS_COMPACT);
     tile_prune_column_device(T, thr.p, o.t, s);
     clock.end();

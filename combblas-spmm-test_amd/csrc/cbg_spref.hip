@@ -22,8 +22,7 @@
 #include <chrono>
 #include <cstring>
 
-#include "cbg_device.h"
-#include "cbg_internal.h"
+#include "cbg_rebuild.h"
 
 namespace cbg {
 
@@ -40,14 +39,6 @@ constexpr int SORT_WAVE_MAX = 256;
 // behind the other blocks' LDS passes.  4096 would halve that for columns R-MAT rarely has.
 constexpr int SORT_LDS_MAX = 2048;
 constexpr int PAD_KEY = 0x7FFFFFFF;  // sorts after every row id (local rows < 2^31 - 1)
-
-inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
-unsigned long long low_bits(int64_t maxval) {  // mask of the bits of values in [0, maxval]
-  unsigned long long m = 0;
-  while ((unsigned long long)std::max<int64_t>(maxval, 0) > m) m = (m << 1) | 1ull;
-  return m;
-}
 
 // ---------------------------------------------------------------------------
 // column stage
@@ -69,12 +60,6 @@ __global__ void k_sel_len(int64_t nsel, const int64_t* __restrict__ sel, const i
   len[j] = cnt[(int64_t)q * stride + lc];
 }
 
-// dense column map of a tile: pos[c] = index of column c in jc (pos preset to -1)
-__global__ void k_col_pos(int64_t nzc, const int32_t* __restrict__ jc, int32_t* __restrict__ pos) {
-  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (k < nzc) pos[jc[k]] = (int32_t)k;
-}
-
 // one wave per requested column: the columns that rank q owns are copied from its tile
 __global__ __launch_bounds__(256) void k_sel_copy(int64_t nsel, const int64_t* __restrict__ sel, int q, int64_t per,
                                                   int np, const int32_t* __restrict__ pos,
@@ -91,23 +76,6 @@ __global__ __launch_bounds__(256) void k_sel_copy(int64_t nsel, const int64_t* _
   for (int64_t i = lane_id(); i < len; i += WAVE) {
     st_stream(oir + dst + i, ld_stream(ir + a + i));
     st_stream(oval + dst + i, ld_stream(val + a + i));
-  }
-}
-
-// ---------------------------------------------------------------------------
-// dense column offsets -> DCSC (empty columns leave jc)
-// ---------------------------------------------------------------------------
-__global__ void k_flag_cols(int64_t n, const int64_t* __restrict__ cp, int64_t* __restrict__ flag) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) flag[i] = cp[i + 1] > cp[i];
-}
-__global__ void k_compact_cols(int64_t n, const int64_t* __restrict__ cp, const int32_t* __restrict__ ids,
-                               const int64_t* __restrict__ pos, int32_t* __restrict__ ojc,
-                               int64_t* __restrict__ ocp) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n && cp[i + 1] > cp[i]) {
-    ojc[pos[i]] = ids ? ids[i] : (int32_t)i;
-    ocp[pos[i]] = cp[i];
   }
 }
 
@@ -141,38 +109,38 @@ __global__ __launch_bounds__(256) void k_expand_count(int64_t nzc, const int64_t
   if (lane_id() == 0) len[k] = s;
 }
 
-// one wave per stored column: every entry writes its list's rows at the column's running offset
-__global__ __launch_bounds__(256) void k_expand_write(int64_t nzc, const int64_t* __restrict__ cp,
-                                                      const int32_t* __restrict__ ir, const double* __restrict__ val,
-                                                      int64_t row0, const int32_t* __restrict__ cnt,
-                                                      const int64_t* __restrict__ start,
-                                                      const int32_t* __restrict__ list,
-                                                      const int64_t* __restrict__ ocp, int32_t* __restrict__ oir,
-                                                      double* __restrict__ oval) {
-  const int64_t k = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  if (k >= nzc) return;
-  const int64_t a = cp[k], b = cp[k + 1];
-  int64_t dst = ocp[k];
-  for (int64_t i0 = a; i0 < b; i0 += WAVE) {  // the trip count is the wave's: no lane leaves early
-    const int64_t i = i0 + lane_id();
-    int64_t r = 0;
-    int c = 0;
-    double v = 0.0;
-    if (i < b) {
-      r = row0 + ld_stream(ir + i);
-      c = cnt[r];
-      v = ld_stream(val + i);
+// a wave per stored column: every entry writes its list's rows at the column's running offset
+struct EmitExpanded {
+  const int64_t* cp;
+  const int32_t* ir;
+  const double* val;
+  int64_t row0;
+  const int32_t* cnt;
+  const int64_t* start;
+  const int32_t* list;
+  __device__ __forceinline__ void operator()(int64_t k, int64_t dst, int32_t* oir, double* oval) const {
+    const int64_t a = cp[k], b = cp[k + 1];
+    for (int64_t i0 = a; i0 < b; i0 += WAVE) {  // the trip count is the wave's: no lane leaves early
+      const int64_t i = i0 + lane_id();
+      int64_t r = 0;
+      int c = 0;
+      double v = 0.0;
+      if (i < b) {
+        r = row0 + ld_stream(ir + i);
+        c = cnt[r];
+        v = ld_stream(val + i);
+      }
+      const int incl = wave_incl_scan(c);
+      const int64_t at = dst + (incl - c);
+      const int64_t from = c ? start[r] : 0;
+      for (int t = 0; t < c; ++t) {
+        st_stream(oir + at + t, list[from + t]);
+        st_stream(oval + at + t, v);
+      }
+      dst += wave_last(incl);
     }
-    const int incl = wave_incl_scan(c);
-    const int64_t at = dst + (incl - c);
-    const int64_t from = c ? start[r] : 0;
-    for (int t = 0; t < c; ++t) {
-      st_stream(oir + at + t, list[from + t]);
-      st_stream(oval + at + t, v);
-    }
-    dst += wave_last(incl);
   }
-}
+};
 
 // ---------------------------------------------------------------------------
 // column sort
@@ -377,8 +345,7 @@ void spref_sel_copy(const cbg_tile& src, int q, int64_t per, int np, const int64
                     const int64_t* ocp, int32_t* oir, double* oval, hipStream_t s) {
   if (nsel == 0 || src.nzc == 0) return;
   DBuf<int32_t> pos(std::max<int64_t>(src.n, 1));
-  CBG_HIP(hipMemsetAsync(pos.p, 0xff, sizeof(int32_t) * src.n, s));
-  hipLaunchKernelGGL(k_col_pos, dim3(nblk(src.nzc, 256)), dim3(256), 0, s, src.nzc, src.jc, pos.p);
+  tile_col_map(src, pos.p, nullptr, s);
   hipLaunchKernelGGL(k_sel_copy, dim3(nblk(nsel * WAVE, 256)), dim3(256), 0, s, nsel, sel, q, per, np, pos.p, src.cp,
                      src.ir, src.val, ocp, oir, oval);
   CBG_HIP(hipStreamSynchronize(s));  // pos is released
@@ -388,30 +355,16 @@ void spref_sel_copy(const cbg_tile& src, int q, int64_t per, int np, const int64
 // ids: the column ids of the ncols offsets (NULL: 0, 1, ...)
 void spref_compact(int64_t m, int64_t n, const int32_t* ids, int64_t ncols, const int64_t* cp, DBuf<int32_t>& ir,
                    DBuf<double>& val, int64_t nnz, cbg_tile& out, hipStream_t s) {
-  DBuf<int64_t> flag(ncols + 1), pos(ncols + 1);
-  if (ncols > 0) hipLaunchKernelGGL(k_flag_cols, dim3(nblk(ncols, 256)), dim3(256), 0, s, ncols, cp, flag.p);
-  exclusive_scan_i64(flag.p, pos.p, ncols, s);
-  int64_t nzc = 0;
-  CBG_HIP(hipMemcpyAsync(&nzc, pos.p + ncols, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  out = cbg_tile{};
-  out.m = m;
-  out.n = n;
-  out.nnz = nnz;
-  out.nzc = nzc;
-  out.on_device = 1;
-  DBuf<int64_t> ocp(nzc + 1);
-  DBuf<int32_t> ojc(std::max<int64_t>(nzc, 1));
   if (ir.n == 0) ir.reset(1);
   if (val.n == 0) val.reset(1);
-  if (ncols > 0)
-    hipLaunchKernelGGL(k_compact_cols, dim3(nblk(ncols, 256)), dim3(256), 0, s, ncols, cp, ids, pos.p, ojc.p, ocp.p);
-  CBG_HIP(hipMemcpyAsync(ocp.p + nzc, &nnz, sizeof(int64_t), hipMemcpyHostToDevice, s));
+  DeferredFree df;
+  TileGuard o;
+  compact_columns(m, n, nnz, ncols, ids, cp, o.t, s, df);
   CBG_HIP(hipStreamSynchronize(s));
-  out.cp = ocp.detach();
-  out.jc = ojc.detach();
-  out.ir = ir.detach();
-  out.val = val.detach();
+  df.synced = true;
+  o.t.ir = ir.detach();
+  o.t.val = val.detach();
+  out = o.release();
 }
 
 // the requested columns sel[0 .. nsel) (device, global ids) of ONE tile that holds them all
@@ -453,20 +406,12 @@ void spref_build_inverse(const int64_t* ri_host, int64_t n, int64_t gm, RowInver
 void spref_expand_rows(const cbg_tile& X, int64_t row0, const RowInverse& inv, int64_t new_m, cbg_tile& out,
                        hipStream_t s) {
   const int64_t nzc = X.nzc;
-  DBuf<int64_t> len(nzc + 1), ocp(nzc + 1);
+  DBuf<int64_t> len(nzc + 1);
   if (nzc)
     hipLaunchKernelGGL(k_expand_count, dim3(nblk(nzc * WAVE, 256)), dim3(256), 0, s, nzc, X.cp, X.ir, row0, inv.cnt.p,
                        len.p);
-  exclusive_scan_i64(len.p, ocp.p, nzc, s);
-  int64_t nnz = 0;
-  CBG_HIP(hipMemcpyAsync(&nnz, ocp.p + nzc, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  DBuf<int32_t> oir(std::max<int64_t>(nnz, 1));
-  DBuf<double> oval(std::max<int64_t>(nnz, 1));
-  if (nzc && nnz)
-    hipLaunchKernelGGL(k_expand_write, dim3(nblk(nzc * WAVE, 256)), dim3(256), 0, s, nzc, X.cp, X.ir, X.val, row0,
-                       inv.cnt.p, inv.start.p, inv.list.p, ocp.p, oir.p, oval.p);
-  spref_compact(new_m, X.n, X.jc, nzc, ocp.p, oir, oval, nnz, out, s);
+  tile_from_columns(new_m, X.n, nzc, X.jc, len.p,
+                    EmitExpanded{X.cp, X.ir, X.val, row0, inv.cnt.p, inv.start.p, inv.list.p}, out, s);
 }
 
 // rows ascending in every column of t, values carried, in place

@@ -386,29 +386,9 @@ static bool redist_fault(cbg_grid* g) {
   return false;
 }
 
-// code of a failure inside a collective step (the step's exception is not
-// rethrown: the caller must still reach the next agree()); the first message
-// of the calling thread is kept for cbg_last_error()
-std::string& step_error() {
+std::string& step_error() {  // see step() in cbg_internal.h
   static thread_local std::string m;
   return m;
-}
-template <class F>
-static int step(F&& f) {
-  try {
-    f();
-    return CBG_OK;
-  } catch (const HipError& e) {
-    if (std::getenv("CBG_DEBUG_ERRORS")) std::fprintf(stderr, "[cbg] %s\n", e.what());
-    if (step_error().empty()) step_error() = e.what();
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    if (step_error().empty()) step_error() = "host allocation failed";
-    return CBG_ERR_OOM;
-  } catch (const std::exception& e) {  // anything else still reaches the next agree()
-    if (step_error().empty()) step_error() = e.what();
-    return CBG_ERR_HIP;
-  }
 }
 
 // Broadcast a tile within a row/col communicator (BCastMatrix: the essentials
@@ -1365,16 +1345,10 @@ int grid_block_extract(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, i
   T0 += lo;
   T1 += lo;
   auto cut = [&](const cbg_tile& X, int64_t a, int64_t b, cbg_tile& piece) {  // local range [a, b) of X
-    TileGuard head, rest, tail;
-    if (dim == 0) {
-      tile_split_rows(X, b, head.t, tail.t, cs);
-      tail = TileGuard();
-      tile_split_rows(head.t, a, rest.t, piece, cs);
-    } else {
-      tile_split_cols(X, b, head.t, tail.t, cs);
-      tail = TileGuard();
-      tile_split_cols(head.t, a, rest.t, piece, cs);
-    }
+    if (dim == 0)
+      tile_slice_rows(X, a, b, piece, cs);
+    else
+      tile_slice_cols(X, a, b, piece, cs);
   };
   // my slice of [lo, hi)
   const int64_t x0 = std::max(S0, lo), x1 = std::max(x0, std::min(S1, hi));

@@ -4,8 +4,7 @@
 //   SpDCCols::Split / Dcsc::Split      SpDCCols.cpp:905-930, dcsc.cpp:1100-1138
 //   B row split by Transpose/Split/Transpose (ParFriends.h:824-829) -> tile_split_rows
 //   SpDCCols::Merge / Dcsc::Merge      SpDCCols.cpp:1194-1223, dcsc.cpp:1204-1230
-#include "cbg_device.h"
-#include "cbg_internal.h"
+#include "cbg_rebuild.h"
 
 namespace cbg {
 
@@ -318,7 +317,18 @@ DevicePool& pool() {
 // ----------------------------------------------------------------------------
 constexpr int SCAN_BS = 256, SCAN_IPT = 8, SCAN_TILE = SCAN_BS * SCAN_IPT;
 
-template <class TI>
+// what element i of the scan is: the input itself, or whether an offsets array steps at i
+struct ScanValue {
+  template <class TI>
+  __device__ __forceinline__ long long operator()(const TI* in, int64_t i) const {
+    return (long long)in[i];
+  }
+};
+struct ScanStep {
+  __device__ __forceinline__ long long operator()(const int64_t* off, int64_t i) const { return off[i + 1] > off[i]; }
+};
+
+template <class TI, class LD = ScanValue>
 __global__ __launch_bounds__(SCAN_BS) void k_scan_tile(const TI* __restrict__ in, int64_t n, int64_t* __restrict__ out,
                                                        int64_t* __restrict__ tile_sum) {
   __shared__ long long wsum[SCAN_BS / WAVE + 1];
@@ -328,7 +338,7 @@ __global__ __launch_bounds__(SCAN_BS) void k_scan_tile(const TI* __restrict__ in
   long long s = 0;
 #pragma unroll
   for (int k = 0; k < SCAN_IPT; ++k) {
-    v[k] = (base + k < n) ? (long long)in[base + k] : 0;
+    v[k] = (base + k < n) ? LD()(in, base + k) : 0;
     s += v[k];
   }
   long long incl = wave_incl_scan64(s);
@@ -363,7 +373,7 @@ __global__ void k_scan_add(int64_t* __restrict__ out, int64_t n, const int64_t* 
   if (i == 0) out[n] = toff[nt];
 }
 
-template <class TI>
+template <class TI, class LD = ScanValue>
 static void scan_impl(const TI* in, int64_t* out, int64_t n, hipStream_t s, DeferredFree* df) {
   const int64_t nt = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (nt <= 1) {
@@ -371,11 +381,11 @@ static void scan_impl(const TI* in, int64_t* out, int64_t n, hipStream_t s, Defe
       CBG_HIP(hipMemsetAsync(out, 0, sizeof(int64_t), s));
       return;
     }
-    hipLaunchKernelGGL(k_scan_tile<TI>, dim3(1), dim3(SCAN_BS), 0, s, in, n, out, out + n);
+    hipLaunchKernelGGL((k_scan_tile<TI, LD>), dim3(1), dim3(SCAN_BS), 0, s, in, n, out, out + n);
     return;
   }
   DBuf<int64_t> sums(nt), offs(nt + 1);
-  hipLaunchKernelGGL(k_scan_tile<TI>, dim3((unsigned)nt), dim3(SCAN_BS), 0, s, in, n, out, sums.p);
+  hipLaunchKernelGGL((k_scan_tile<TI, LD>), dim3((unsigned)nt), dim3(SCAN_BS), 0, s, in, n, out, sums.p);
   scan_impl<int64_t>(sums.p, offs.p, nt, s, df);
   hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n, offs.p, nt);
   if (df) {  // released when the caller's work on `s` has been synchronized
@@ -391,6 +401,20 @@ void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t 
 }
 void exclusive_scan_i32_to_i64(const int32_t* in, int64_t* out, int64_t n, hipStream_t s, DeferredFree* df) {
   scan_impl<int32_t>(in, out, n, s, df);
+}
+void scan_nonempty(const int64_t* off, int64_t* pos, int64_t n, hipStream_t s, DeferredFree* df) {
+  scan_impl<int64_t, ScanStep>(off, pos, n, s, df);
+}
+
+__global__ void k_gather_words(const int64_t* a, const int64_t* b, const int64_t* c, int64_t* out) {
+  out[0] = *a;
+  out[1] = *b;
+  out[2] = c ? *c : 0;
+}
+void read_words(const int64_t* a, const int64_t* b, const int64_t* c, int64_t* dev3, int64_t* host3, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_words, dim3(1), dim3(1), 0, s, a, b, c, dev3);
+  CBG_HIP(hipMemcpyAsync(host3, dev3, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  CBG_HIP(hipStreamSynchronize(s));
 }
 
 // ----------------------------------------------------------------------------
@@ -484,84 +508,44 @@ void tile_split_cols(const cbg_tile& T, int64_t cut, cbg_tile& L, cbg_tile& R, h
 }
 
 // ----------------------------------------------------------------------------
-// row split: per column, rows < cut go to Top, rows >= cut (re-based) to Bot
+// row split: rows < cut go to Top, rows >= cut (re-based) to Bot: two row slices
 // ----------------------------------------------------------------------------
-__global__ void k_rowsplit_count(int64_t nzc, const int64_t* __restrict__ cp, const int32_t* __restrict__ ir, int cut,
-                                 int64_t* __restrict__ ntop, int64_t* __restrict__ nbot, int64_t* __restrict__ ftop,
-                                 int64_t* __restrict__ fbot) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= nzc) return;
-  const int64_t a = cp[i], b = cp[i + 1];  // 64-bit: tiles may hold 2^31 or more entries
-  const int64_t k = lower_bound_g64(ir, a, b, cut) - a;
-  ntop[i] = k;
-  nbot[i] = (b - a) - k;
-  ftop[i] = k > 0;
-  fbot[i] = (b - a - k) > 0;
-}
-__global__ void k_rowsplit_copy(int64_t nzc, const int64_t* __restrict__ cp, const int32_t* __restrict__ jc,
-                                const int32_t* __restrict__ ir, const double* __restrict__ val, int cut,
-                                const int64_t* __restrict__ otop, const int64_t* __restrict__ obot,
-                                const int64_t* __restrict__ ctop, const int64_t* __restrict__ cbot,
-                                int32_t* __restrict__ tjc, int64_t* __restrict__ tcp, int32_t* __restrict__ tir,
-                                double* __restrict__ tval, int32_t* __restrict__ bjc, int64_t* __restrict__ bcp,
-                                int32_t* __restrict__ bir, double* __restrict__ bval) {
-  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  if (i >= nzc) return;
-  const int lane = lane_id();
-  const int64_t a = cp[i], b = cp[i + 1];
-  const int64_t k = otop[i + 1] - otop[i];
-  if (k > 0) {
-    if (lane == 0) {
-      tjc[ctop[i]] = jc[i];
-      tcp[ctop[i]] = otop[i];
-    }
-    for (int64_t q = lane; q < k; q += WAVE) {
-      tir[otop[i] + q] = ir[a + q];
-      tval[otop[i] + q] = val[a + q];
-    }
-  }
-  const int64_t r = (b - a) - k;
-  if (r > 0) {
-    if (lane == 0) {
-      bjc[cbot[i]] = jc[i];
-      bcp[cbot[i]] = obot[i];
-    }
-    for (int64_t q = lane; q < r; q += WAVE) {
-      bir[obot[i] + q] = ir[a + k + q] - cut;
-      bval[obot[i] + q] = val[a + k + q];
-    }
-  }
+void tile_split_rows(const cbg_tile& T, int64_t cut, cbg_tile& Top, cbg_tile& Bot, hipStream_t s) {
+  TileGuard top;
+  tile_slice_rows(T, 0, cut, top.t, s);
+  tile_slice_rows(T, cut, T.m, Bot, s);
+  Top = top.release();
 }
 
-void tile_split_rows(const cbg_tile& T, int64_t cut, cbg_tile& Top, cbg_tile& Bot, hipStream_t s) {
-  const int64_t nz = T.nzc;
-  if (nz == 0) {
-    tile_alloc_device(Top, cut, T.n, 0, 0);
-    tile_alloc_device(Bot, T.m - cut, T.n, 0, 0);
-    return;
-  }
-  DBuf<int64_t> ntop(nz + 1), nbot(nz + 1), ftop(nz + 1), fbot(nz + 1);
-  DBuf<int64_t> otop(nz + 1), obot(nz + 1), ctop(nz + 1), cbot(nz + 1);
-  hipLaunchKernelGGL(k_rowsplit_count, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, T.cp, T.ir, (int)cut,
-                     ntop.p, nbot.p, ftop.p, fbot.p);
-  exclusive_scan_i64(ntop.p, otop.p, nz, s);
-  exclusive_scan_i64(nbot.p, obot.p, nz, s);
-  exclusive_scan_i64(ftop.p, ctop.p, nz, s);
-  exclusive_scan_i64(fbot.p, cbot.p, nz, s);
-  int64_t h[4];
-  CBG_HIP(hipMemcpyAsync(&h[0], otop.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&h[1], obot.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&h[2], ctop.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&h[3], cbot.p + nz, 8, hipMemcpyDeviceToHost, s));
+// ----------------------------------------------------------------------------
+// dense exclusive offsets -> the jc/cp of a tile (cbg_rebuild.h, layer a)
+// ----------------------------------------------------------------------------
+__global__ void k_compact_columns(int64_t nslots, const int32_t* __restrict__ ids, const int64_t* __restrict__ off,
+                                  const int64_t* __restrict__ pos, int32_t* __restrict__ jc,
+                                  int64_t* __restrict__ cp) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < nslots) put_column(i, nslots, ids, off, pos, jc, cp);
+}
+
+void compact_columns(int64_t m, int64_t n, int64_t nnz, int64_t nslots, const int32_t* ids, const int64_t* off,
+                     cbg_tile& t, hipStream_t s, DeferredFree& df) {
+  DBuf<int64_t> pos(nslots + 1);
+  scan_nonempty(off, pos.p, nslots, s, &df);
+  int64_t nzc = 0;
+  CBG_HIP(hipMemcpyAsync(&nzc, pos.p + nslots, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   CBG_HIP(hipStreamSynchronize(s));
-  tile_alloc_device(Top, cut, T.n, h[0], h[2]);
-  tile_alloc_device(Bot, T.m - cut, T.n, h[1], h[3]);
-  hipLaunchKernelGGL(k_rowsplit_copy, dim3((unsigned)((nz * WAVE + 255) / 256)), dim3(256), 0, s, nz, T.cp, T.jc, T.ir,
-                     T.val, (int)cut, otop.p, obot.p, ctop.p, cbot.p, Top.jc, Top.cp, Top.ir, Top.val, Bot.jc, Bot.cp,
-                     Bot.ir, Bot.val);
-  CBG_HIP(hipMemcpyAsync(Top.cp + h[2], &h[0], 8, hipMemcpyHostToDevice, s));
-  CBG_HIP(hipMemcpyAsync(Bot.cp + h[3], &h[1], 8, hipMemcpyHostToDevice, s));
-  CBG_HIP(hipStreamSynchronize(s));
+  t.m = m;
+  t.n = n;
+  t.nnz = nnz;
+  t.nzc = nzc;
+  t.on_device = 1;
+  t.cp = static_cast<int64_t*>(pool().alloc(sizeof(int64_t) * (nzc + 1)));
+  t.jc = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(nzc, 1)));
+  if (nslots > 0)
+    hipLaunchKernelGGL(k_compact_columns, dim3(nblk(nslots, 256)), dim3(256), 0, s, nslots, ids, off, pos.p, t.jc, t.cp);
+  else
+    CBG_HIP(hipMemsetAsync(t.cp, 0, sizeof(int64_t), s));
+  df.take(pos);
 }
 
 // ----------------------------------------------------------------------------
@@ -609,18 +593,6 @@ __global__ void k_rowcat_count(int64_t nzc, const int32_t* __restrict__ jc, cons
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < nzc) len[jc[i]] += cp[i + 1] - cp[i];  // one part per launch: no two threads share jc[i]
 }
-__global__ void k_flag_nonzero(int64_t n, const int64_t* __restrict__ len, int64_t* __restrict__ flag) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) flag[i] = len[i] > 0;
-}
-__global__ void k_rowcat_cols(int64_t n, const int64_t* __restrict__ len, const int64_t* __restrict__ pos,
-                              const int64_t* __restrict__ off, int32_t* __restrict__ jc, int64_t* __restrict__ cp) {
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (j < n && len[j] > 0) {
-    jc[pos[j]] = (int32_t)j;
-    cp[pos[j]] = off[j];
-  }
-}
 __global__ void k_rowcat_copy(int64_t nzc, const int32_t* __restrict__ jc, const int64_t* __restrict__ cp,
                               const int32_t* __restrict__ ir, const double* __restrict__ val, int64_t roff,
                               int64_t* __restrict__ fill, int32_t* __restrict__ oir, double* __restrict__ oval) {
@@ -638,7 +610,8 @@ __global__ void k_rowcat_copy(int64_t nzc, const int32_t* __restrict__ jc, const
 
 void tile_concat_rows(const std::vector<cbg_tile>& parts, const std::vector<int64_t>& row_off, int64_t m, int64_t n,
                       cbg_tile& out, hipStream_t s) {
-  DBuf<int64_t> len(n + 1), flag(n + 1), pos(n + 1), off(n + 1);
+  DBuf<int64_t> len(n + 1), off(n + 1);
+  DeferredFree df;  // after the buffers: on a throw it waits for the kernels before they are released
   CBG_HIP(hipMemsetAsync(len.p, 0, sizeof(int64_t) * (n + 1), s));
   int64_t nnz = 0;
   for (auto& p : parts) {
@@ -647,24 +620,21 @@ void tile_concat_rows(const std::vector<cbg_tile>& parts, const std::vector<int6
       hipLaunchKernelGGL(k_rowcat_count, dim3((unsigned)((p.nzc + 255) / 256)), dim3(256), 0, s, p.nzc, p.jc, p.cp,
                          len.p);
   }
-  hipLaunchKernelGGL(k_flag_nonzero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, len.p, flag.p);
-  exclusive_scan_i64(flag.p, pos.p, n, s);
-  exclusive_scan_i64(len.p, off.p, n, s);
-  int64_t nzc = 0;
-  CBG_HIP(hipMemcpyAsync(&nzc, pos.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  tile_alloc_device(out, m, n, nnz, nzc);
-  hipLaunchKernelGGL(k_rowcat_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, len.p, pos.p, off.p, out.jc,
-                     out.cp);
-  CBG_HIP(hipMemcpyAsync(out.cp + nzc, &nnz, sizeof(int64_t), hipMemcpyHostToDevice, s));
-  // `off` doubles as the running fill pointer per column
+  exclusive_scan_i64(len.p, off.p, n, s, &df);
+  TileGuard o;
+  compact_columns(m, n, nnz, n, nullptr, off.p, o.t, s, df);
+  o.t.ir = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
+  o.t.val = static_cast<double*>(pool().alloc(sizeof(double) * std::max<int64_t>(nnz, 1)));
+  // `off` doubles as the running fill pointer per column (the compaction has read it: same stream)
   for (size_t k = 0; k < parts.size(); ++k) {
     const cbg_tile& p = parts[k];
     if (p.nzc > 0)
       hipLaunchKernelGGL(k_rowcat_copy, dim3((unsigned)((p.nzc * WAVE + 255) / 256)), dim3(256), 0, s, p.nzc, p.jc,
-                         p.cp, p.ir, p.val, row_off[k], off.p, out.ir, out.val);
+                         p.cp, p.ir, p.val, row_off[k], off.p, o.t.ir, o.t.val);
   }
   CBG_HIP(hipStreamSynchronize(s));
+  df.synced = true;
+  out = o.release();
 }
 
 // ----------------------------------------------------------------------------
@@ -697,56 +667,31 @@ void tile_slice_cols(const cbg_tile& T, int64_t a, int64_t b, cbg_tile& out, hip
 }
 
 __global__ void k_rowslice_count(int64_t nzc, const int64_t* __restrict__ cp, const int32_t* __restrict__ ir, int lo,
-                                 int hi, int64_t* __restrict__ first, int64_t* __restrict__ cnt,
-                                 int64_t* __restrict__ flag) {
+                                 int hi, int64_t* __restrict__ first, int64_t* __restrict__ cnt) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= nzc) return;
-  const int64_t a = lower_bound_g64(ir, cp[i], cp[i + 1], lo);
+  const int64_t a = lower_bound_g64(ir, cp[i], cp[i + 1], lo);  // 64-bit: tiles may hold 2^31 or more entries
   const int64_t b = lower_bound_g64(ir, a, cp[i + 1], hi);
   first[i] = a;
   cnt[i] = b - a;
-  flag[i] = b > a;
 }
-__global__ void k_rowslice_copy(int64_t nzc, const int32_t* __restrict__ jc, const int32_t* __restrict__ ir,
-                                const double* __restrict__ val, int lo, const int64_t* __restrict__ first,
-                                const int64_t* __restrict__ off, const int64_t* __restrict__ col,
-                                int32_t* __restrict__ ojc, int64_t* __restrict__ ocp, int32_t* __restrict__ oir,
-                                double* __restrict__ oval) {
-  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  if (i >= nzc) return;
-  const int64_t k = off[i + 1] - off[i];
-  if (k == 0) return;
-  if (lane_id() == 0) {
-    ojc[col[i]] = jc[i];
-    ocp[col[i]] = off[i];
+struct EmitRowSlice {  // cnt[i] entries from first[i], rows re-based by lo
+  const int32_t* ir;
+  const double* val;
+  const int64_t *first, *cnt;
+  int lo;
+  __device__ __forceinline__ void operator()(int64_t i, int64_t dst, int32_t* oir, double* oval) const {
+    copy_range(ir, val, first[i], cnt[i], lo, oir, oval, dst);
   }
-  const int64_t a = first[i];
-  for (int64_t q = lane_id(); q < k; q += WAVE) {
-    oir[off[i] + q] = ir[a + q] - lo;
-    oval[off[i] + q] = val[a + q];
-  }
-}
+};
 
 void tile_slice_rows(const cbg_tile& T, int64_t a, int64_t b, cbg_tile& out, hipStream_t s) {
   const int64_t nz = T.nzc;
-  if (nz == 0) {
-    tile_alloc_device(out, b - a, T.n, 0, 0);
-    return;
-  }
-  DBuf<int64_t> first(nz + 1), cnt(nz + 1), flag(nz + 1), off(nz + 1), col(nz + 1);
-  hipLaunchKernelGGL(k_rowslice_count, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, T.cp, T.ir, (int)a,
-                     (int)b, first.p, cnt.p, flag.p);
-  exclusive_scan_i64(cnt.p, off.p, nz, s);
-  exclusive_scan_i64(flag.p, col.p, nz, s);
-  int64_t h[2];
-  CBG_HIP(hipMemcpyAsync(&h[0], off.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&h[1], col.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  tile_alloc_device(out, b - a, T.n, h[0], h[1]);
-  hipLaunchKernelGGL(k_rowslice_copy, dim3((unsigned)((nz * WAVE + 255) / 256)), dim3(256), 0, s, nz, T.jc, T.ir,
-                     T.val, (int)a, first.p, off.p, col.p, out.jc, out.cp, out.ir, out.val);
-  CBG_HIP(hipMemcpyAsync(out.cp + h[1], &h[0], 8, hipMemcpyHostToDevice, s));
-  CBG_HIP(hipStreamSynchronize(s));
+  DBuf<int64_t> first(nz + 1), cnt(nz + 1);
+  if (nz > 0)
+    hipLaunchKernelGGL(k_rowslice_count, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, T.cp, T.ir, (int)a, (int)b, first.p,
+                       cnt.p);
+  tile_from_columns(b - a, T.n, nz, T.jc, cnt.p, EmitRowSlice{T.ir, T.val, first.p, cnt.p, (int)a}, out, s);
 }
 
 // ----------------------------------------------------------------------------
@@ -929,6 +874,22 @@ void tile_counts_device(const cbg_tile& t, int dim, int32_t* d, int64_t padded, 
   CBG_HIP(hipStreamSynchronize(s));  // the comm stream reads the counts next
 }
 
+// dense column map: pos[j] = position of column j in jc (-1: not stored), len[j] = its length
+__global__ void k_col_map(int64_t nzc, const int64_t* __restrict__ cp, const int32_t* __restrict__ jc,
+                          int32_t* __restrict__ pos, int64_t* __restrict__ len) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= nzc) return;
+  const int32_t j = jc[p];
+  pos[j] = (int32_t)p;
+  if (len) len[j] = cp[p + 1] - cp[p];
+}
+void tile_col_map(const cbg_tile& t, int32_t* pos, int64_t* len, hipStream_t s) {
+  const int64_t n = std::max<int64_t>(t.n, 1);
+  CBG_HIP(hipMemsetAsync(pos, 0xff, sizeof(int32_t) * n, s));
+  if (len) CBG_HIP(hipMemsetAsync(len, 0, sizeof(int64_t) * n, s));
+  if (t.nzc > 0) hipLaunchKernelGGL(k_col_map, dim3(nblk(t.nzc, 256)), dim3(256), 0, s, t.nzc, t.cp, t.jc, pos, len);
+}
+
 // sum over k < K of a[k] * b[k], where a is split into segments aoff[s]..aoff[s+1]
 // stored at a + s * astride (b likewise): the inner index walks A's column
 // blocks and B's row blocks at once
@@ -998,81 +959,59 @@ int64_t blocked_dot_device(const int32_t* a, int64_t astride, const std::vector<
 // tile of a grid row keeps the same rows).  Ids, not positions: R-MAT's ids are
 // scrambled, so either is a uniform sample.
 __global__ void k_sample_col_len(int64_t nzc, int stride, const int64_t* __restrict__ cp, const int32_t* __restrict__ jc,
-                                 int64_t* __restrict__ len, int64_t* __restrict__ flag) {
+                                 int64_t* __restrict__ len) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= nzc) return;
-  const bool keep = jc[i] % stride == 0;
-  len[i] = keep ? cp[i + 1] - cp[i] : 0;
-  flag[i] = keep;
+  if (i < nzc) len[i] = jc[i] % stride == 0 ? cp[i + 1] - cp[i] : 0;
 }
 __global__ void k_sample_row_len(int64_t nzc, int stride, const int64_t* __restrict__ cp,
-                                 const int32_t* __restrict__ ir, int64_t* __restrict__ len, int64_t* __restrict__ flag) {
+                                 const int32_t* __restrict__ ir, int64_t* __restrict__ len) {
   const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
   if (i >= nzc) return;
   int c = 0;
   for (int64_t q = cp[i] + lane_id(); q < cp[i + 1]; q += WAVE) c += ir[q] % stride == 0;
   c = wave_sum(c);
-  if (lane_id() == 0) {
-    len[i] = c;
-    flag[i] = c > 0;
-  }
+  if (lane_id() == 0) len[i] = c;
 }
-// a wave per kept column; rows == true: keep only rows % stride == 0, renumbered
-__global__ void k_sample_copy(int64_t nzc, int stride, bool rows, const int64_t* __restrict__ cp,
-                              const int32_t* __restrict__ jc, const int32_t* __restrict__ ir,
-                              const double* __restrict__ val, const int64_t* __restrict__ len,
-                              const int64_t* __restrict__ off, const int64_t* __restrict__ col,
-                              int64_t* __restrict__ ocp, int32_t* __restrict__ ojc, int32_t* __restrict__ oir,
-                              double* __restrict__ oval) {
-  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  if (i >= nzc || len[i] == 0) return;
-  const int lane = lane_id();
-  if (lane == 0) {
-    ojc[col[i]] = jc[i];
-    ocp[col[i]] = off[i];
+struct EmitWholeColumn {  // a kept column, as it is
+  const int64_t* cp;
+  const int32_t* ir;
+  const double* val;
+  __device__ __forceinline__ void operator()(int64_t i, int64_t dst, int32_t* oir, double* oval) const {
+    copy_range(ir, val, cp[i], cp[i + 1] - cp[i], 0, oir, oval, dst);
   }
-  int64_t dst = off[i];
-  for (int64_t q0 = cp[i]; q0 < cp[i + 1]; q0 += WAVE) {
-    const int64_t q = q0 + lane;
-    const bool in = q < cp[i + 1];
-    const int r = in ? ir[q] : 0;
-    const bool keep = in && (!rows || r % stride == 0);
-    const unsigned long long m = __ballot(keep);
-    if (keep) {
-      const int64_t at = dst + __popcll(m & ((1ull << lane) - 1ull));
-      oir[at] = rows ? r / stride : r;
-      oval[at] = val[q];
-    }
-    dst += __popcll(m);
+};
+struct EmitSampledRows {  // the rows that are multiples of stride, renumbered row / stride
+  const int64_t* cp;
+  const int32_t* ir;
+  const double* val;
+  int stride;
+  struct Keep {
+    static constexpr bool by_row = true;
+    int stride;
+    __device__ __forceinline__ bool operator()(int32_t r) const { return r % stride == 0; }
+  };
+  struct Row {
+    int stride;
+    __device__ __forceinline__ int32_t operator()(int32_t r) const { return r / stride; }
+  };
+  __device__ __forceinline__ void operator()(int64_t i, int64_t dst, int32_t* oir, double* oval) const {
+    copy_filtered(ir, val, cp[i], cp[i + 1] - cp[i], Keep{stride}, Row{stride}, oir, oval, dst);
   }
-}
-static void tile_sample(const cbg_tile& T, int stride, bool rows, cbg_tile& out, hipStream_t s) {
-  const int64_t m = rows ? (T.m + stride - 1) / stride : T.m;
+};
+void tile_sample_cols(const cbg_tile& T, int stride, cbg_tile& out, hipStream_t s) {
   const int64_t nz = T.nzc;
-  if (nz == 0) {
-    tile_alloc_device(out, m, T.n, 0, 0);
-    return;
-  }
-  DBuf<int64_t> len(nz + 1), flag(nz + 1), off(nz + 1), col(nz + 1);
-  if (rows)
-    hipLaunchKernelGGL(k_sample_row_len, dim3((unsigned)((nz * WAVE + 255) / 256)), dim3(256), 0, s, nz, stride, T.cp,
-                       T.ir, len.p, flag.p);
-  else
-    hipLaunchKernelGGL(k_sample_col_len, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, s, nz, stride, T.cp, T.jc,
-                       len.p, flag.p);
-  exclusive_scan_i64(len.p, off.p, nz, s);
-  exclusive_scan_i64(flag.p, col.p, nz, s);
-  int64_t h[2];
-  CBG_HIP(hipMemcpyAsync(&h[0], off.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&h[1], col.p + nz, 8, hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
-  tile_alloc_device(out, m, T.n, h[0], h[1]);
-  hipLaunchKernelGGL(k_sample_copy, dim3((unsigned)((nz * WAVE + 255) / 256)), dim3(256), 0, s, nz, stride, rows, T.cp,
-                     T.jc, T.ir, T.val, len.p, off.p, col.p, out.cp, out.jc, out.ir, out.val);
-  CBG_HIP(hipMemcpyAsync(out.cp + h[1], &h[0], 8, hipMemcpyHostToDevice, s));
-  CBG_HIP(hipStreamSynchronize(s));
+  DBuf<int64_t> len(nz + 1);
+  if (nz > 0)
+    hipLaunchKernelGGL(k_sample_col_len, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, stride, T.cp, T.jc, len.p);
+  tile_from_columns(T.m, T.n, nz, T.jc, len.p, EmitWholeColumn{T.cp, T.ir, T.val}, out, s);
 }
-void tile_sample_cols(const cbg_tile& T, int stride, cbg_tile& out, hipStream_t s) { tile_sample(T, stride, false, out, s); }
-void tile_sample_rows(const cbg_tile& T, int stride, cbg_tile& out, hipStream_t s) { tile_sample(T, stride, true, out, s); }
+void tile_sample_rows(const cbg_tile& T, int stride, cbg_tile& out, hipStream_t s) {
+  const int64_t nz = T.nzc;
+  DBuf<int64_t> len(nz + 1);
+  if (nz > 0)
+    hipLaunchKernelGGL(k_sample_row_len, dim3(nblk(nz * WAVE, 256)), dim3(256), 0, s, nz, stride, T.cp, T.ir, len.p);
+  tile_from_columns((T.m + stride - 1) / stride, T.n, nz, T.jc, len.p, EmitSampledRows{T.cp, T.ir, T.val, stride}, out,
+                    s);
+}
 
 }  // namespace cbg

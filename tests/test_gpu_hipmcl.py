@@ -201,6 +201,50 @@ def test_chaos_exact_on_dyadic(cbg, grid):
 # ---------------------------------------------------------------------------
 # loops
 # ---------------------------------------------------------------------------
+def _loops_long_case():
+    """300 x 300 with columns of more than one 64-lane round around their diagonal: 150 stores it
+    at position 65 of 130, 200 at position 64 of 130, 100 (65 entries) lacks it and gains it at
+    position 64 with one entry behind; short columns beside them"""
+    cols = {150: list(range(85, 215)), 200: list(range(136, 266)), 100: list(range(36, 100)) + [200],
+            3: [3], 7: [1, 299], 299: [0, 150]}
+    row = [r for j in sorted(cols) for r in cols[j]]
+    col = [j for j in sorted(cols) for _ in cols[j]]
+    return hr.from_coo(300, 300, row, col, (np.arange(len(row)) % 97 + 1) / 128.0)
+
+
+@pytest.mark.parametrize("n", [1, 4, 5, 2048, 2049, "long"])
+def test_loops_slot_counts(cbg, grid, n):
+    """the same on n dense columns: one slot that is first and last at once and holds only its
+    loop (1: RemoveLoops gives the empty tile, AddLoops fills a tile that stores nothing), a wave
+    per column in blocks of four (4, 5), the column scan's one tile and its second level (2048,
+    2049), where columns 0 and n - 1 store nothing, so the first and the last slot gain an entry
+    under AddLoops and stay empty under RemoveLoops; long: the dropped, replaced or inserted entry
+    at position 64 and 65 of a column, entries behind it (_loops_long_case)"""
+    if n == "long":
+        t = _loops_long_case()
+    elif n == 1:
+        t = hr.from_coo(1, 1, [0], [0], [0.5])
+    elif n <= 16:
+        t = hr.from_coo(n, n, [1, 2, 2, 1], [1, 1, 2, n - 2], [0.5, 0.25, 0.125, 0.75])
+    else:
+        t = hr.loops_case(seed=n, n=n)
+    n = t["n"]
+    A = _mat(cbg, grid, t)
+    want, removed = hr.remove_loops(t)
+    assert A.RemoveLoops() == removed > 0
+    assert A.tile.digest()["unsorted"] == 0
+    assert_tiles_bits_equal(A.tile.to_host(), want)
+    if n == 1:
+        assert removed == 1 and A.tile.nnz == 0 and A.tile.nzc == 0
+    lv = (np.arange(n) + 1) / 64.0
+    for src in (t, want):
+        for replace in (True, False):
+            B = _mat(cbg, grid, src)
+            B.AddLoops(lv, replace)
+            assert B.tile.digest()["unsorted"] == 0 and B.tile.nzc == n
+            assert_tiles_bits_equal(B.tile.to_host(), hr.add_loops(src, lv, replace))
+
+
 def test_loops_against_restatement(cbg, grid):
     t = hr.loops_case()
     n = t["n"]

@@ -529,6 +529,19 @@ def test_auto_phases_plan(cbg):
             # sampled and the estimate is close to the true nnz(C)
             assert plan["phases"] >= 4 and plan["c_budget_bytes"] < 1.2e9, plan
             assert 0.8 * gd["nnz"] <= plan["nnz_est"] <= 1.3 * gd["nnz"], plan
+            # the sample exactly: B's columns whose id is a multiple of 256, built on the host;
+            # the estimate is its compression in plan_phases' own double arithmetic
+            b = B.tile.to_host()
+            keep = b["jc"] % 256 == 0
+            cnt = np.diff(b["cp"])
+            ent = np.repeat(keep, cnt)
+            sample = dict(m=b["m"], n=b["n"], cp=np.concatenate([[0], np.cumsum(cnt[keep])]).astype(np.int64),
+                          jc=b["jc"][keep], ir=b["ir"][ent], val=b["val"][ent])
+            assert 0 < keep.sum() < len(keep)
+            S = cbg.Tile.from_dict(sample)
+            fs, zs = cbg.LocalSymbolic(A.tile, S)
+            S.free()
+            assert plan["nnz_est"] == int(min(1.0, 1.1 * zs / fs) * plan["flops"]), (plan, fs, zs)
         else:
             # the flops bound (12 B x 1.1e9) fits the device: one phase, no sample taken
             assert plan["phases"] == 1 and plan["nnz_est"] == plan["flops"], plan

@@ -127,20 +127,37 @@ def test_col_stats_strict_and_not(cbg):
     np.testing.assert_array_equal(cnt, mcl_ref.col_stats_ref(t, np.full(t["n"], mcl_ref.H), 1)[0])
 
 
-def test_prune_column_emptied_columns(cbg):
-    t = _big()
+def _prune_emptied(cbg, t):
+    """the first, the last, a middle column emptied, several, none (nothing pruned at all), all"""
     T = cbg.Tile.from_dict(t)
     jc = t["jc"]
     nzc = len(jc)
-    for emptied in ([0], [nzc - 1], [nzc // 2], [0, 1, nzc // 2, nzc - 2, nzc - 1], list(range(nzc))):
-        thr = np.full(t["n"], mcl_ref.H)
+    several = sorted({0, min(1, nzc - 1), nzc // 2, max(nzc - 2, 0), nzc - 1})
+    for emptied in ([0], [nzc - 1], [nzc // 2], several, [], list(range(nzc))):
+        thr = np.full(t["n"], mcl_ref.H if emptied else -1e300)
         thr[jc[emptied]] = 1e300
         out = T.prune_column(thr)
         want = mcl_ref.prune_columns(t, thr[jc])
         assert out.digest()["unsorted"] == 0
         assert out.nzc == len(want["jc"]) and out.nnz == len(want["ir"])
         assert_tiles_bits_equal(out.to_host(), want)
+        if not emptied:
+            assert_tiles_bits_equal(want, t)
     assert out.nnz == 0 and out.nzc == 0  # the all-pruned tile is the empty tile
+
+
+def test_prune_column_emptied_columns(cbg):
+    """on the big case, and on 1, 4, 5, 2048 and 2049 stored columns of 1, 63, 64, 65 and 130
+    entries (a wave, a block of four waves and one more, the slot scan's second level; the
+    64-lane ballot round of the filtered copy)"""
+    import tile_ops_ref
+    for k in tile_ops_ref.REBUILD_SLOTS:
+        _prune_emptied(cbg, tile_ops_ref.rebuild_case(k))
+    t = _big()
+    T = cbg.Tile.from_dict(t)
+    jc = t["jc"]
+    nzc = len(jc)
+    _prune_emptied(cbg, t)
     # thresholds of the columns' own values: entries equal to the threshold stay
     thr = np.zeros(t["n"])
     for p, j in enumerate(jc):

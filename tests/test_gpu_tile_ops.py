@@ -221,7 +221,9 @@ def test_tile_equal_structure(cbg):
 # g. splits, concatenation and slices
 # --------------------------------------------------------------------------
 def _split_tiles():
-    return [("gaps", R.split_case()), ("single_col", R.single_col_case())]
+    """the last five: the column-rebuild primitive's slot counts (tile_ops_ref.rebuild_case)"""
+    return [("gaps", R.split_case()), ("single_col", R.single_col_case())] + [
+        (f"slots{k}", R.rebuild_case(k)) for k in R.REBUILD_SLOTS]
 
 
 def _col_cuts(d):
@@ -234,7 +236,10 @@ def _col_cuts(d):
 def _row_cuts(d):
     lo, hi = int(d["ir"].min()), int(d["ir"].max())
     mid = int(np.sort(d["ir"])[len(d["ir"]) // 2])
-    return sorted({0, d["m"], mid, mid + 1, hi + 1, hi, lo, lo + 1})
+    # just past the first column's last row, and the last column's first row: in a rebuild_case
+    # these empty the first (the last) column alone on one side, every other one on the other
+    past_first, at_last = int(d["ir"][d["cp"][1] - 1]) + 1, int(d["ir"][d["cp"][-2]])
+    return sorted({0, d["m"], mid, mid + 1, hi + 1, hi, lo, lo + 1, past_first, at_last})
 
 
 def test_split_cols_cuts(cbg):

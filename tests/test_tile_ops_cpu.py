@@ -39,6 +39,16 @@ def test_dense_round_trip_and_generators():
     d = R.split_case()
     assert sorted(np.diff(d["cp"]).tolist()) == sorted(R.SPLIT_LENS * 2) and len(np.setdiff1d(np.arange(d["n"]), d["jc"]))
     assert 0 < d["ir"].min() and d["ir"].max() + 1 < d["m"]
+    for nzc in R.REBUILD_SLOTS:
+        d = R.rebuild_case(nzc)
+        lens = np.diff(d["cp"])
+        assert len(d["jc"]) == nzc and R.unsorted_host(d) == 0 and len(d["ir"]) < 4000
+        assert nzc < 7 or set(R.SPLIT_LENS) <= set(lens.tolist())
+        assert lens[0] == 1 and d["ir"][0] < 200 and (nzc == 1 or (lens[-1] == 65 and d["ir"][d["cp"][-2]] >= 400))
+        assert nzc < 3 or (200 <= d["ir"][1:d["cp"][-2]].min() and d["ir"][1:d["cp"][-2]].max() < 400)
+        top, bot = H.split_rows_host(d, 200)
+        assert len(top["jc"]) == 1 and len(bot["jc"]) == nzc - 1
+        assert len(np.setdiff1d(np.arange(int(d["jc"][0]) + 1, d["n"]), d["jc"]))  # a gap above the first id
 
 
 def test_transpose_host_against_dense():

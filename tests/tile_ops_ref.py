@@ -10,14 +10,14 @@ import numpy as np
 from helpers import DBL_MAX, INF, dcsc_from_cols, tile_cols
 
 # --------------------------------------------------------------------------
-# the radix sort's pass rule (csrc/cbg_ops.hip low_bits, csrc/cbg_sort.hip)
+# the radix sort's pass rule (csrc/cbg_internal.h low_bits, csrc/cbg_sort.hip)
 # --------------------------------------------------------------------------
 SORT_TILE = 4096   # csrc/cbg_sort.hip RS_TILE
 SCAN_TILE = 2048   # csrc/cbg_tile.hip SCAN_TILE
 
 
 def low_bits(maxval):
-    """mask of the bits of values in [0, maxval] (csrc/cbg_ops.hip low_bits)"""
+    """mask of the bits of values in [0, maxval] (csrc/cbg_internal.h low_bits)"""
     m = 0
     while maxval > m:
         m = (m << 1) | 1
@@ -284,6 +284,28 @@ def split_case(seed=31, m=400, n=40):
 def single_col_case(seed=32, m=400, n=40):
     rng = np.random.default_rng(seed)
     return cols_tile(rng, m, n, [70], ids=[17], lo=5, hi=m - 5)
+
+
+REBUILD_SLOTS = (1, 4, 5, SCAN_TILE, SCAN_TILE + 1)   # stored columns: one wave, a 256-thread block of four
+# waves and one more, the slot scan's one tile and its second level (csrc/cbg_rebuild.h)
+
+
+def rebuild_case(nzc, seed=41, m=600):
+    """nzc stored columns at ids with gaps: the first of length 1 with its row in [5, 200), the
+    last (nzc > 1) of length 65 in [400, 595), the ones between in [200, 400) with the
+    lengths SPLIT_LENS, then 1 or 2.  A row cut at 200 or 400 empties exactly the first or
+    the last column on one side and every other column on the other."""
+    rng = np.random.default_rng(seed + nzc)
+    n = 2 * nzc + 3
+    ids = np.sort(rng.choice(n, nzc, replace=False))
+    mid = [SPLIT_LENS[i] if i < len(SPLIT_LENS) else 1 + i % 2 for i in range(max(nzc - 2, 0))]
+    lens = ([1] + mid + [65])[:nzc] if nzc > 1 else [1]
+    cols = [np.zeros(0, np.int64)] * n
+    for p, (j, L) in enumerate(zip(ids, lens)):
+        lo = 5 if p == 0 else 400 if p == nzc - 1 else 200
+        cols[int(j)] = lo + np.sort(rng.choice(195, int(L), replace=False))
+    nnz = int(np.sum(lens))
+    return dcsc_from_cols(m, n, cols, (rng.permutation(nnz) + 1.0) * (1.0 / 1024) - 1.0)
 
 
 def block_case(seed=33, m=23, n=19, nnz=30):
