@@ -5,7 +5,8 @@ A matrix is a DCSC dict (m, n, cp, jc, ir, val) of the WHOLE distributed matrix.
 The multiply comes from helpers' CPU oracle, the pruning from mcl_ref, the connected
 components are a union-find with the library's canonical labels (labels[v] = the
 rank of v's component, components ordered by their smallest vertex).  Column sums
-are np.sum's: bit-equal to the device only where the sums are exact (dyadic values)."""
+are np.sum's: bit-equal to the device only where the sums are exact (dyadic values);
+tests/colsum_ref.py restates the device's own sum order, for inexact values."""
 import numpy as np
 
 import mcl_ref

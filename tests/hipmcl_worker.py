@@ -13,7 +13,11 @@ The fused Inflate is compared by bits with the four-call composition on the same
 grid; against the 1 x 1 result it can differ in the last bits (the normalised values
 are not dyadic and a column's sum is split between the ranks), so that comparison
 allows the sums' rounding -- except on grids of one row (1 x 2), where no column is
-split and the bits must be equal.  The phased SUMMA on a block-diagonal matrix (empty
+split and the bits must be equal.  On inexact values (colsum_ref.split_case: per-rank lengths
+at the class bounds of the column sums, columns empty in one row block) the four reductions,
+MakeColStochastic, Chaos and Inflate(2.0) have the bits of the order-exact restatement summed
+row block by row block and combined in rank order (tests/colsum_ref.py) -- on two row blocks
+not the bits of the 1 x 1 run, which the restatement itself shows.  The phased SUMMA on a block-diagonal matrix (empty
 off-diagonal tiles on 2 x 2) equals the 1 x 1 product by bits.  HipMCL on both golden
 cases: the 1 x 1 partition and iteration count.  Prints HIPMCLOK per rank.
 """
@@ -26,6 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from conftest import load_cbg  # noqa: E402
 from helpers import assert_tiles_bits_equal  # noqa: E402
+import colsum_ref as cr  # noqa: E402
 import hipmcl_ref as hr  # noqa: E402
 import mcl_ref  # noqa: E402
 
@@ -107,6 +112,33 @@ def main():
         lens = np.repeat(hr.reduce_cols(tp, "count")[c0:c1][got["jc"]], np.diff(got["cp"]))
         assert np.all(np.abs(got["val"] - want["val"]) <= 4 * lens * np.finfo(np.float64).eps * want["val"])
         assert abs(cf - cw) <= 4 * 30000 * np.finfo(np.float64).eps * max(cw, 1.0)
+
+    # ---- inexact values: the bits of the order-exact restatement, row block by row block
+    for pattern in ("uniform", "normal"):
+        x = cr.split_case(pattern)
+        cuts = [cbg.block_range(x["m"], pr, i)[0] for i in range(1, pr)]
+        assert (cuts == [x["m"] // 2]) if pr == 2 else not cuts
+        c0, c1 = cbg.block_range(x["n"], pc, grid.pcol)
+        D = cbg.SpParMat.from_global(grid, x)
+        for what, ident in (("sum", 0.0), ("sum", -3.0), ("sumsq", 0.0), ("max", 0.0), ("max", -1e300), ("count", 0.0)):
+            got, want = D.Reduce(cbg.Column, what, ident), cr.reduce_cols_ordered(x, what, ident, cuts)
+            assert np.array_equal(bits(got), bits(want[c0:c1])), (rank, pattern, what, ident)
+            if pr == 2 and what in ("sum", "sumsq"):  # not the 1 x 1 run's bits: the split shows
+                assert not np.array_equal(bits(want), bits(cr.reduce_cols_ordered(x, what, ident)))
+        assert bits([D.Chaos()])[0] == bits([cr.chaos_ordered(x, cuts)])[0], (rank, pattern)
+        if pattern != "uniform":
+            continue
+        D.MakeColStochastic()
+        want = cr.make_col_stochastic_ordered(x, cuts)
+        assert_tiles_bits_equal(D.tile.to_host(), mine(want))
+        F = cbg.SpParMat.from_global(grid, x)
+        cf = F.Inflate(2.0)
+        want, wc = cr.inflate_ordered(x, 2.0, cuts=cuts)
+        assert bits([cf])[0] == bits([wc])[0], (rank, cf, wc)
+        assert_tiles_bits_equal(F.tile.to_host(), mine(want))
+        if pr == 2:
+            whole, _ = cr.inflate_ordered(x, 2.0)
+            assert not np.array_equal(bits(want["val"]), bits(whole["val"]))
 
     # ---- loops and connected components (square matrices)
     for sq in (hr.loops_case(), hr.loops_case(seed=8, n=41), hr.planted()):

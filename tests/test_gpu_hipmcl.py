@@ -1,6 +1,8 @@
 """The HipMCL iteration on device (csrc/cbg_mcl.hip, the loop in csrc/cbg_summa.cpp)
 against the NumPy restatement (tests/hipmcl_ref.py).  Where the inputs' sums are exact
-(dyadic values) results are compared by bits.
+(dyadic values) results are compared by bits; on inexact values the column sums, moments
+and the inflation are compared by bits with the order-exact restatement (tests/colsum_ref.py,
+whose own checks are in tests/test_colsum_cpu.py).
 
 Tolerances (measured, see DESIGN.md "HipMCL iteration"):
   POW_ULP   device pow against numpy.power over the 109419 values of test_apply_pow: the
@@ -21,6 +23,7 @@ import sys
 import numpy as np
 import pytest
 
+import colsum_ref as cr
 import hipmcl_ref as hr
 import mcl_ref
 from helpers import assert_tiles_bits_equal
@@ -196,6 +199,147 @@ def test_inflate_fused_equals_composed(cbg, grid, power):
 def test_chaos_exact_on_dyadic(cbg, grid):
     t = _big()
     assert _mat(cbg, grid, t).Chaos() == hr.chaos(t)
+
+
+# ---------------------------------------------------------------------------
+# inexact values: the bits of the order-exact restatement (tests/colsum_ref.py)
+# ---------------------------------------------------------------------------
+def _assert_bits_or_nan(got, want, msg=""):
+    """equal bits, and a NaN exactly where the restatement has one"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=str(msg))
+    ok = ~np.isnan(want)
+    bad = np.flatnonzero(_bits(got[ok]) != _bits(want[ok]))
+    assert len(bad) == 0, (msg, "first of %d:" % len(bad), int(np.flatnonzero(ok)[bad[0]]), got[ok][bad[0]].hex(),
+                           want[ok][bad[0]].hex())
+
+
+def _assert_cols_bits(t, got, want, msg):
+    """dense per-column results by bits; reports the first failing (length, got, want)"""
+    bad = np.flatnonzero(_bits(got) != _bits(want))
+    lens = cr.column_lengths(t)
+    assert len(bad) == 0, (msg, "%d columns differ; first: length %d, got %s, want %s" % (
+        len(bad), lens[bad[0]], float(got[bad[0]]).hex(), float(want[bad[0]]).hex()))
+
+
+def _assert_vals_bits(t, got, want, msg):
+    assert np.array_equal(got["cp"], want["cp"]) and np.array_equal(got["ir"], want["ir"])
+    bad = np.flatnonzero(_bits(got["val"]) != _bits(want["val"]))
+    lens = np.repeat(np.diff(t["cp"]), np.diff(t["cp"]))
+    assert len(bad) == 0, (msg, "%d values differ; first: column length %d, got %s, want %s" % (
+        len(bad), lens[bad[0]] if len(bad) else 0, float(got["val"][bad[0]]).hex(), float(want["val"][bad[0]]).hex()))
+
+
+REDUCTIONS = (("sum", 0.0), ("sum", -7.5), ("sumsq", 0.0), ("sumsq", 3.0), ("max", 0.0), ("max", -1e300),
+              ("count", 0.0), ("count", 9.0))
+
+
+@pytest.mark.parametrize("pattern", cr.PATTERNS)
+def test_reduce_cols_ordered_bits(cbg, grid, pattern):
+    t = cr.inexact_case(pattern)
+    A = _mat(cbg, grid, t)
+    for what, ident in REDUCTIONS:
+        got = A.Reduce(cbg.Column, what, ident)
+        _assert_cols_bits(t, got, cr.reduce_cols_ordered(t, what, ident), (pattern, what, ident))
+    again = A.Reduce(cbg.Column, "sum", 0.0)  # the same bits in every run
+    np.testing.assert_array_equal(_bits(again), _bits(A.Reduce(cbg.Column, "sum", 0.0)))
+    _assert_cols_bits(t, again, cr.reduce_cols_ordered(t, "sum"), (pattern, "again"))
+
+
+@pytest.mark.parametrize("pattern", ["uniform", "wide"])
+def test_make_col_stochastic_ordered_bits(cbg, grid, pattern):
+    t = cr.inexact_case(pattern)
+    A = _mat(cbg, grid, t)
+    A.MakeColStochastic()
+    _assert_vals_bits(t, A.tile.to_host(), cr.make_col_stochastic_ordered(t), pattern)
+
+
+@pytest.mark.parametrize("pattern", cr.PATTERNS)
+def test_chaos_ordered_bits(cbg, grid, pattern):
+    t = cr.inexact_case(pattern)
+    got, want = _mat(cbg, grid, t).Chaos(), cr.chaos_ordered(t)
+    assert _bits([got])[0] == _bits([want])[0], (pattern, float(got).hex(), float(want).hex())
+    if pattern == "uniform":  # a stochastic matrix's chaos: the figure the loop watches
+        s = cr.make_col_stochastic_ordered(t)
+        got, want = _mat(cbg, grid, s).Chaos(), cr.chaos_ordered(s)
+        assert want > 0.0 and _bits([got])[0] == _bits([want])[0], (float(got).hex(), float(want).hex())
+
+
+@pytest.mark.parametrize("pattern", ["uniform", "wide"])
+def test_inflate_square_ordered_bits(cbg, grid, pattern):
+    t = cr.inexact_case(pattern)
+    A = _mat(cbg, grid, t)
+    c = A.Inflate(2.0)
+    want, wc = cr.inflate_ordered(t, 2.0)
+    assert _bits([c])[0] == _bits([wc])[0], (pattern, float(c).hex(), float(wc).hex())
+    _assert_vals_bits(t, A.tile.to_host(), want, pattern)
+
+
+def test_inflate_power_ordered_bits(cbg, grid):
+    """the device's pow cannot be restated by bits, so it is taken from the device: v = val * inv
+    is computed here, raised to 1.7 by Apply, and the sums and the scaling are finished here"""
+    t = cr.inexact_case("uniform")
+
+    def device_pow(v):
+        P = _mat(cbg, grid, dict(t, val=v))
+        P.Apply("pow", 1.7)
+        return P.tile.to_host()["val"]
+
+    want, wc = cr.inflate_ordered(t, 1.7, pow_fn=device_pow)
+    A = _mat(cbg, grid, t)
+    c = A.Inflate(1.7)
+    assert _bits([c])[0] == _bits([wc])[0], (float(c).hex(), float(wc).hex())
+    _assert_vals_bits(t, A.tile.to_host(), want, "1.7")
+
+
+def test_special_value_columns(cbg, grid):
+    """+inf, a sum that cancels to exactly 0, subnormal sums, DBL_MIN and -0.0 entries in each
+    length class, under IEEE rules"""
+    t, cases = cr.special_case()
+    A = _mat(cbg, grid, t)
+    for what, ident in REDUCTIONS:
+        _assert_bits_or_nan(A.Reduce(cbg.Column, what, ident), cr.reduce_cols_ordered(t, what, ident), (what, ident))
+    got, want = A.Chaos(), cr.chaos_ordered(t)
+    assert _bits([got])[0] == _bits([want])[0], (got, want)
+    for strict in (1, 0):  # thr 0: -0.0 is kept only when not strict, its sum +0.0 either way
+        cnt, tot = A.tile.col_stats(0.0, strict)
+        wc, ws = cr.col_stats_ordered(t, np.zeros(t["n"]), strict)
+        np.testing.assert_array_equal(cnt, wc)
+        _assert_bits_or_nan(tot, ws, ("col_stats", strict))
+    A.MakeColStochastic()
+    g, w = A.tile.to_host(), cr.make_col_stochastic_ordered(t)
+    _assert_bits_or_nan(g["val"], w["val"], "MakeColStochastic")
+    # the restatement holds what the cases are about
+    by = {c: w["val"][t["cp"][p]:t["cp"][p + 1]] for p, c in enumerate(cases)}
+    src = {c: t["val"][t["cp"][p]:t["cp"][p + 1]] for p, c in enumerate(cases)}
+    sums = cr.reduce_cols_ordered(t, "sum")[t["jc"]]
+    for p, (kind, ln) in enumerate(cases):
+        v = by[(kind, ln)]
+        if kind == "inf":
+            assert sums[p] == np.inf and np.isnan(v).sum() == 1 and np.all(v[~np.isnan(v)] == 0.0)
+        elif kind == "cancel":
+            assert _bits([sums[p]])[0] == 0 and np.all(np.abs(v[3:]) == hr.DBL_MAX) and v[0] == np.inf
+        elif kind == "subnormal":
+            assert 0.0 < sums[p] < hr.DBL_MIN and np.all(v == np.inf)
+        elif kind == "dbl_min":
+            assert sums[p] == ln * hr.DBL_MIN and np.all(np.abs(v * ln - 1.0) < 1e-14)
+        else:
+            assert _bits([sums[p]])[0] == 0 and np.all(_bits(v) == _bits([-0.0])[0]) and np.all(src[(kind, ln)] == 0)
+
+
+@pytest.mark.parametrize("nnz", [1, 2, 3, 4, 517])
+def test_apply_pow_unaligned_head(cbg, nnz):
+    """k_apply_pow's head path: a val that starts 8 bytes off a 16-byte boundary, as a borrowed
+    view of a tile's entries from its second one on"""
+    import ctypes
+    rng = np.random.default_rng(nnz)
+    v = rng.uniform(0.5, 2.0, nnz + 1)
+    base = cbg.Tile.from_dict(hr.from_coo(nnz + 1, 1, np.arange(nnz + 1), np.zeros(nnz + 1), v))
+    assert base.c.val % 16 == 0
+    view = cbg.CTile(base.c.m, 1, nnz, 1, base.c.cp, base.c.jc, base.c.ir + 4, base.c.val + 8, 1, 0)
+    assert cbg.lib().cbg_tile_apply(ctypes.byref(view), cbg.APPLY_POW, 2.0) == 0
+    got = base.to_host()["val"]
+    np.testing.assert_array_equal(_bits(got), _bits(np.concatenate([v[:1], v[1:] * v[1:]])))
 
 
 # ---------------------------------------------------------------------------

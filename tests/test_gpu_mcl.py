@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import colsum_ref as cr
 import mcl_ref
 from helpers import assert_tiles_bits_equal, load_npz
 from test_multiprocess import free_port
@@ -125,6 +126,32 @@ def test_col_stats_strict_and_not(cbg):
     assert differ - 2 * s1 >= len(t["jc"])  # every column holds its threshold at least once
     cnt, tot = T.col_stats(mcl_ref.H, 1)  # one value for all columns
     np.testing.assert_array_equal(cnt, mcl_ref.col_stats_ref(t, np.full(t["n"], mcl_ref.H), 1)[0])
+
+
+@pytest.mark.parametrize("pattern", cr.PATTERNS)
+def test_col_stats_ordered_bits(cbg, pattern):
+    """inexact values: counts and sums of the kept values by bits against the order-exact
+    restatement (tests/colsum_ref.py); the threshold is the column's own median, so the kept
+    set is a strict subset and the strict and the non-strict result differ"""
+    t = cr.inexact_case(pattern)
+    T = cbg.Tile.from_dict(t)
+    thr = np.zeros(t["n"])
+    for p, j in enumerate(t["jc"]):
+        c = t["val"][t["cp"][p]:t["cp"][p + 1]]
+        thr[j] = np.sort(c)[len(c) // 2]
+    lens = cr.column_lengths(t)
+    res = {}
+    for strict in (1, 0):
+        cnt, tot = T.col_stats(thr, strict)
+        wc, ws = cr.col_stats_ordered(t, thr, strict)
+        np.testing.assert_array_equal(cnt, wc)
+        bad = np.flatnonzero(tot.view(np.uint64) != ws.view(np.uint64))
+        assert len(bad) == 0, (pattern, strict, "%d columns differ; first: length %d, got %s, want %s" % (
+            len(bad), lens[bad[0]], float(tot[bad[0]]).hex(), float(ws[bad[0]]).hex()))
+        assert np.all(cnt[lens > 1] < lens[lens > 1])  # a strict subset is kept
+        res[strict] = (cnt, tot)
+    assert np.all(res[0][0][lens > 0] > res[1][0][lens > 0])
+    assert np.any(res[0][1].view(np.uint64) != res[1][1].view(np.uint64))
 
 
 def _prune_emptied(cbg, t):
