@@ -15,53 +15,29 @@ constexpr int EMPTY_KEY = 0x7FFFFFFF;  // empty hash slot; sorts after every row
 
 // streaming stores/loads for data written or read once (C's entries, the kept
 // symbolic bitmaps): nontemporal, so they do not evict A's rows from L2
-#ifndef CBG_NT_OUT
-#define CBG_NT_OUT 1  // +2.8 % at scale 22, +6 % at 18 (same-box A/B)
-#endif
-#ifndef CBG_NT_EMIT
-#define CBG_NT_EMIT 1  // hash-slab emit stores too: +0.3 % at 22
-#endif
+// (+2.8 % at scale 22, +6 % at 18, same-box A/B)
 template <class T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
-#if CBG_NT_OUT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 template <class T>
 __device__ __forceinline__ T ld_stream(const T* p) {
-#if CBG_NT_OUT
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 // 16-byte nontemporal store / load of 4 words (p 16-byte aligned)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_stream4(unsigned* p, uint4 v) {
   u32x4 x = {v.x, v.y, v.z, v.w};
-#if CBG_NT_OUT
   __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(p));
-#else
-  *reinterpret_cast<u32x4*>(p) = x;
-#endif
 }
 __device__ __forceinline__ uint4 ld_stream4(const unsigned* p) {
-#if CBG_NT_OUT
   const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#else
-  const u32x4 x = *reinterpret_cast<const u32x4*>(p);
-#endif
   return make_uint4(x.x, x.y, x.z, x.w);
 }
+// the hash-slab emit's stores are nontemporal too: +0.3 % at 22
 template <class T>
 __device__ __forceinline__ void st_emit(T* p, T v) {
-#if CBG_NT_EMIT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 // Order LDS traffic between the lanes of ONE wave (LDS executes a wave's
@@ -280,15 +256,10 @@ __device__ __forceinline__ void block_products(const int* pref, int total, S&& s
 }
 
 // Staged segments: st[sg] holds A's start minus the segment's first product
-// index (CBG_SEG_OFF=1), so a segment switch reads one LDS word less
-#ifndef CBG_SEG_OFF
-#define CBG_SEG_OFF 1
-#endif
-__device__ __forceinline__ int seg_stage(int s, int ex) { return CBG_SEG_OFF ? s - ex : s; }
-__device__ __forceinline__ int seg_off(const int* st, const int* pref, int sg) {
-  return CBG_SEG_OFF ? st[sg] : st[sg] - pref[sg];
-}
-// per-segment register cache: A offset (st[sg] - pref[sg]) and B value
+// index, so a segment switch reads one LDS word less (+0.7 % at 22, +2.4 % at 18)
+__device__ __forceinline__ int seg_stage(int s, int ex) { return s - ex; }
+__device__ __forceinline__ int seg_off(const int* st, const int* pref, int sg) { return st[sg]; }
+// per-segment register cache: A offset (A's start minus the first product index) and B value
 struct SegI {
   int off;
 };
@@ -394,13 +365,9 @@ __device__ __forceinline__ void bitonic_sort_kv(int* keys, double* vals, int tid
 // (quad_perm for 1 and 2, row_half_mirror + quad reversal for 4, row_ror:8
 // for 8) and gfx950's permlane swaps across rows (16, 32).  A __shfl_xor is a
 // ds_bpermute: an LDS instruction shared by the CU's four SIMDs, which the
-// wave sorts issued ~1200 of per wave (CBG_XOR_DPP=0 restores them).
-#ifndef CBG_XOR_DPP
-#define CBG_XOR_DPP 1
-#endif
+// wave sorts issued ~1200 of per wave.
 template <int D>
 __device__ __forceinline__ int xor_lane(int v) {
-#if CBG_XOR_DPP
   if constexpr (D == 1) {
     return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
   } else if constexpr (D == 2) {
@@ -420,9 +387,6 @@ __device__ __forceinline__ int xor_lane(int v) {
     const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
     return (threadIdx.x & 32) ? (int)r[0] : (int)r[1];
   }
-#else
-  return __shfl_xor(v, D);
-#endif
 }
 template <int D>
 __device__ __forceinline__ double xor_lane(double v) {
@@ -469,19 +433,14 @@ __device__ __forceinline__ void wave_bitonic_sort_kv(int& key, double& val, int 
 // and each entry's position inside its bucket is its rank among the few
 // entries of that bucket.  O(T + n * bucket size) work, 3 barriers.
 // Scratch: boff[NB+1], cur[NB] ints, members[n] (slot ids).
-#ifndef CBG_EMIT_STAGE
-#define CBG_EMIT_STAGE 0  // staged coalesced emit: -1.7 % at 22, -0.8 % at 18 (same box, 2 runs): scattered stores kept
-#endif
-template <int T, int BS, int NB, bool MOFF = false, bool STAGE = (CBG_EMIT_STAGE != 0)>
+// The entries leave with one scattered store each (staging them through the
+// table for coalesced stores: -1.7 % at 22, -0.8 % at 18, same box, 2 runs).
+template <int T, int BS, int NB>
 __device__ __forceinline__ void hash_emit_sorted(int* keys, double* vals, int lo, int bshift, int* boff,
                                                  int* cur, unsigned short* members, int* tmp,
                                                  int32_t* __restrict__ out_ir, double* __restrict__ out_val,
-                                                 int64_t obase, unsigned short* moff = nullptr) {
-  // MOFF: pass 2 also stores each entry's row offset inside its bucket
-  // ((key - lo) mod 2^bshift, < 2^16), so the rank loop reads one u16 per
-  // bucket member instead of a slot id and then that slot's key
+                                                 int64_t obase) {
   const int tid = threadIdx.x;
-  const int omask = (1 << bshift) - 1;
   for (int b = tid; b < NB; b += BS) cur[b] = 0;
   __syncthreads();
   for (int j = tid; j < T; j += BS) {
@@ -501,71 +460,27 @@ __device__ __forceinline__ void hash_emit_sorted(int* keys, double* vals, int lo
   __syncthreads();
   for (int j = tid; j < T; j += BS) {
     const int k = keys[j];
-    if (k != EMPTY_KEY) {
-      const int pos = atomicAdd(&cur[(k - lo) >> bshift], 1);
-      members[pos] = (unsigned short)j;
-      if (MOFF) moff[pos] = (unsigned short)((k - lo) & omask);
-    }
+    if (k != EMPTY_KEY) members[atomicAdd(&cur[(k - lo) >> bshift], 1)] = (unsigned short)j;
   }
   __syncthreads();
-  auto rank_of = [&](int k) {
-    const int b = (k - lo) >> bshift;
-    int r = boff[b];
-    const int e = boff[b + 1];
-    if (MOFF) {
-      const int mo = (k - lo) & omask;
-      for (int q = boff[b]; q < e; ++q) r += (int)moff[q] < mo;
-    } else {
-      for (int q = boff[b]; q < e; ++q) r += keys[members[q]] < k;
-    }
-    return r;
-  };
-  // STAGE: every thread holds its entries' (rank, row, value) in registers,
-  // then the table itself is overwritten in rank order and copied out with
-  // coalesced stores (instead of one scattered store per entry); tables up
-  // to load 2/3 (more entries: the scattered stores)
-  constexpr int E = (2 * T / 3 + BS - 1) / BS;
-  if (STAGE && total <= E * BS) {
-    int rr[E], kk[E];
-    double vv[E];
-#pragma unroll
-    for (int q = 0; q < E; ++q) {
-      const int p = tid + q * BS;
-      rr[q] = -1;
-      if (p < total) {
-        const int j = members[p];
-        kk[q] = keys[j];
-        vv[q] = vals[j];
-        rr[q] = rank_of(kk[q]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < E; ++q)
-      if (rr[q] >= 0) {
-        keys[rr[q]] = kk[q];
-        vals[rr[q]] = vv[q];
-      }
-    __syncthreads();
-    for (int p = tid; p < total; p += BS) {
-      st_emit(&out_ir[obase + p], keys[p]);
-      st_emit(&out_val[obase + p], vals[p]);
-    }
-    return;
-  }
   for (int p = tid; p < total; p += BS) {
     const int j = members[p];
     const int k = keys[j];
-    const int r = rank_of(k);
+    const int b = (k - lo) >> bshift;
+    int r = boff[b];
+    const int e = boff[b + 1];
+    for (int q = boff[b]; q < e; ++q) r += keys[members[q]] < k;
     st_emit(&out_ir[obase + r], k);
     st_emit(&out_val[obase + r], vals[j]);
   }
 }
 
-// The same emit (MOFF) with each thread's slots kept in registers between the
-// counting and the scatter pass: the counting pass's returning atomic gives
-// every entry its index inside its bucket, so the scatter pass re-reads no key
-// and needs no second atomic.  The rank pass still walks the bucket-ordered
+// The same emit with each entry's row offset inside its bucket ((key - lo) mod
+// 2^bshift, < 2^16) cached in moff, so the rank loop reads one u16 per bucket
+// member instead of a slot id and then that slot's key, and with each thread's
+// slots kept in registers between the counting and the scatter pass: the
+// counting pass's returning atomic gives every entry its index inside its
+// bucket, so the scatter pass re-reads no key and needs no second atomic.  The rank pass still walks the bucket-ordered
 // list (its output stores then land nearly in order: ranking each thread's
 // own slots instead scatters the stores over the slab, 2.3x slower).
 template <int T, int BS, int NB>

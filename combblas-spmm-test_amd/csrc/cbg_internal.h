@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -184,6 +185,15 @@ struct DeferredFree {
     if (pool().quarantine()) pool().quarantine_release();
   }
 };
+
+// blocks of `per` items that cover n items; at least one (a grid of 0 blocks is refused)
+inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
+// kernels that take more than 64 KiB of dynamic LDS have to say so
+template <class K>
+void set_lds(K kernel, size_t bytes) {
+  if (bytes > 65536)
+    CBG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
 
 // local SpGEMM (cbg_local.hip)
 struct LocalStats {

@@ -10,7 +10,7 @@
 //   k_flops_seg   flops per B column               (estimateFLOP, mtSpGEMM.h:1056-1134)
 //   classify/bin  columns binned by flops
 //   k_sym_*       exact nnz per C column            (estimateNNZ_Hash, mtSpGEMM.h:805-933)
-//                 wave-level LDS hash (F<=512), block LDS hash (F<=4096),
+//                 expand-sort-compress waves (F<=512, with their numeric), block LDS hash (F<=4096),
 //                 LDS bitmap over row passes for big columns (+ slab plan)
 //   scan          column pointers of C              (prefixsum, mtSpGEMM.h:23-70)
 //   k_num_*       numeric: LDS hash accumulate + in-LDS bitonic sort (small/medium),
@@ -260,16 +260,18 @@ constexpr int BIN_ITEMS = 16;
 // thin_R > 0: big columns with flops * THIN_RATIO < B entries * thin_R go to
 // thin_bin (mode 0) / are skipped like the fused ones (mode 1)
 constexpr int64_t THIN_RATIO = 4;
-// copy1: a column with one B entry and 0 < flops <= big is C(:,j) = A(:,k) * b,
-// nnz = flops: mode 0 writes cnt and bins it with the empty columns, mode 1
-// skips it (k_copy_single writes it)
+// a column with one B entry and flops > 0 is C(:,j) = A(:,k) * b, nnz = flops:
+// mode 0 writes cnt and bins it with the empty columns, mode 1 skips it
+// (k_copy_single / k_copy_single_big write it; also those of more than `big`
+// flops -- R-MAT columns whose one entry hits a hub -- instead of (column,
+// panel) pairs: s22 446.4 -> 440.9 ms)
 // low (mode 0, 0 = off): the lower big-column cut the host may still choose once it has
 // the histogram (BinRemap).  For the columns of low < flops <= big, lo_stats gets their B
 // entries ([0] the ones that stay big, [1] the ones the lower cut makes thin) and the thin
 // ones' count and flops ([2], [3]); a thin one's bin byte carries BIN_THIN_LOW.
 constexpr int BIN_THIN_LOW = 0x80;
 __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __restrict__ flops,
-                                                  int32_t* __restrict__ cnt, int mode, int copy1, int64_t big, BinThr thr,
+                                                  int32_t* __restrict__ cnt, int mode, int64_t big, BinThr thr,
                                                   uint8_t* __restrict__ bin, int* __restrict__ hist,
                                                   int64_t fused_max, const int64_t* __restrict__ cpB, int big_bin,
                                                   unsigned long long* __restrict__ big_entries,
@@ -299,7 +301,7 @@ __global__ __launch_bounds__(256) void k_classify(int64_t n, const int64_t* __re
       // thin big columns (cbg_thin.hip): few products per B entry, so the R
       // (column, panel) pairs would each stage the whole column for little
       const bool thin = thin_R > 0 && f > big && f * THIN_RATIO < (cpB[i + 1] - cpB[i]) * (int64_t)thin_R;
-      const bool single = copy1 && f > 0 && (f <= big || copy1 > 1) && cpB[i + 1] - cpB[i] == 1;
+      const bool single = f > 0 && cpB[i + 1] - cpB[i] == 1;
       // numeric bins: big columns last; columns computed by the fused small-column
       // pass (0 < flops <= fused_max), the thin pass or the single-entry copy in
       // bin 0, which the numeric skips
@@ -467,58 +469,8 @@ __device__ __forceinline__ int lane_rank(unsigned long long m) {
 }
 
 // ----------------------------------------------------------------------------
-// symbolic: wave per column, LDS hash of row ids
+// symbolic: block per column, LDS hash of row ids
 // ----------------------------------------------------------------------------
-template <int LOGT>
-struct SymWaveLds {
-  static constexpr int T = 1 << LOGT;
-  static constexpr int INTS = T + (WAVE + 4) + WAVE;  // keys, pref[65]+pad, st[64]
-};
-
-template <int LOGT>
-__global__ __launch_bounds__(256) void k_sym_wave(const int32_t* __restrict__ perm, int n,
-                                                  const int64_t* __restrict__ cpB, const int32_t* __restrict__ irB,
-                                                  const int2* __restrict__ cmap, const int32_t* __restrict__ irA,
-                                                  int32_t* __restrict__ cnt) {
-  constexpr int T = 1 << LOGT;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int w = threadIdx.x / WAVE, lane = lane_id();
-  int* keys = reinterpret_cast<int*>(smem) + w * SymWaveLds<LOGT>::INTS;
-  int* pref = keys + T;
-  int* st = pref + WAVE + 4;
-  const int idx = blockIdx.x * (blockDim.x / WAVE) + w;
-  if (idx >= n) return;
-  const int col = perm[idx];
-  for (int j = lane; j < T; j += WAVE) keys[j] = EMPTY_KEY;
-  const int64_t p1 = cpB[col + 1];
-  int count = 0;
-  for (int64_t c0 = cpB[col]; c0 < p1; c0 += WAVE) {
-    const int64_t p = c0 + lane;
-    int s = 0, len = 0;
-    if (p < p1) {
-      int2 e = cmap[irB[p]];
-      s = e.x;
-      len = e.y;
-    }
-    const int incl = wave_incl_scan(len);
-    const int total = wave_last(incl);
-    pref[lane + 1] = incl;
-    if (lane == 0) pref[0] = 0;
-    st[lane] = seg_stage(s, incl - len);
-    wave_sync();
-    wave_products(
-        pref, WAVE, 0, total, [&](int sg) { return SegI{seg_off(st, pref, sg)}; },
-        [&](const SegI& g, int u) { return irA[g.off + u]; },
-        [&](int row) {
-          count += hash_claim(keys, hash_slot<LOGT>(row), T - 1, row);
-        });
-    wave_sync();
-  }
-  count = wave_sum(count);
-  if (lane == 0) cnt[col] = count;
-}
-
-// symbolic: block per column
 template <int LOGT, int BS>
 struct SymBlockLds {
   static constexpr int T = 1 << LOGT;
@@ -792,12 +744,10 @@ struct SymPanelLds {
   int* tmp;      // scan scratch [BIG_BS / WAVE + 4]; tmp[NW + 3]: overflow count
   int* ovf;      // [SYM_OVF_CAP] rows deferred by hash_claim_bounded
 };
-#ifndef CBG_SYM_OVF  // probes of a symbolic hash insert before it is deferred (0: unbounded)
-#define CBG_SYM_OVF 2
-#endif
+constexpr int SYM_NPROBE = 2;  // probes of a symbolic hash insert before it is deferred
 // rows of the symbolic overflow list: what is left of 160 KiB / 4 blocks per
 // CU after the 8192-word bitmap and the staging arrays (the launch keeps 4 blocks)
-constexpr int SYM_OVF_CAP = CBG_SYM_OVF > 0 ? 896 : 0;
+constexpr int SYM_OVF_CAP = 896;
 static_assert(SYM_OVF_CAP >= NFINE_MAX + 2, "the cut pass keeps a pair's slab rows in the overflow list");
 
 // hash_claim with at most NPROBE probes; a row without a slot by then goes to
@@ -1167,17 +1117,12 @@ __device__ __forceinline__ bool sym_group(const SymPanelArgs& a, const SymPanelL
       [&](const SegI& g, int u) { return irA[g.off + u]; },
       [&](int row) {
         const unsigned h = ((unsigned)row * 0x9E3779B1u) & mask;
-        if (CBG_SYM_OVF > 0)
-          count += hash_claim_bounded<CBG_SYM_OVF>(keys, h, mask, row, ocount, L.ovf, SYM_OVF_CAP);
-        else
-          count += hash_claim(keys, h, mask, row);
+        count += hash_claim_bounded<SYM_NPROBE>(keys, h, mask, row, ocount, L.ovf, SYM_OVF_CAP);
       });
   hook(2);
-  if (CBG_SYM_OVF > 0) {
-    __syncthreads();
-    const int no = *ocount;
-    if (no > 0) count += hash_claim_drain<CBG_SYM_OVF>(keys, mask, L.ovf, min(no, SYM_OVF_CAP));
-  }
+  __syncthreads();
+  const int no = *ocount;
+  if (no > 0) count += hash_claim_drain<SYM_NPROBE>(keys, mask, L.ovf, min(no, SYM_OVF_CAP));
   count = wave_sum(count);
   if (lane_id() == 0 && count) atomicAdd(&L.fine[0], count);
   __syncthreads();
@@ -1205,16 +1150,9 @@ __device__ __forceinline__ bool sym_group(const SymPanelArgs& a, const SymPanelL
 }
 
 // grid: RG groups x (columns of the class) in XCD column order (k_sym_panel)
-#ifndef CBG_SYM_WPE  // waves per SIMD k_sym_panel is compiled for (0: the compiler's choice)
-// 8: at most 64 VGPRs, so 4 blocks of 512 threads per CU (the LDS allows 4; at
-// 65 VGPRs only 3 fit): +4.2 % at scale 22 (profiles/r04_ab_hash_sym.json)
-#define CBG_SYM_WPE 8
-#endif
-#if CBG_SYM_WPE > 0
-#define CBG_SYM_WPE_ATTR __attribute__((amdgpu_waves_per_eu(CBG_SYM_WPE)))
-#else
-#define CBG_SYM_WPE_ATTR
-#endif
+// k_sym_panel is compiled for 8 waves per SIMD: at most 64 VGPRs, so 4 blocks of
+// 512 threads per CU (the LDS allows 4; at 65 VGPRs only 3 fit): +4.2 % at
+// scale 22 (profiles/r04_ab_hash_sym.json)
 __device__ __forceinline__ SymPanelLds sym_lds(char* smem, int hwords) {
   SymPanelLds L;
   L.bm = reinterpret_cast<unsigned*>(smem);
@@ -1228,7 +1166,7 @@ __device__ __forceinline__ SymPanelLds sym_lds(char* smem, int hwords) {
 // GROUPS: the launch's units span several panels (sym_group); false for the
 // single-panel class, whose kernel then carries no group code (fewer spills)
 template <bool GROUPS>
-__global__ __launch_bounds__(BIG_BS) CBG_SYM_WPE_ATTR void k_sym_panel(SymPanelArgs a) {
+__global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) void k_sym_panel(SymPanelArgs a) {
   // Persistent blocks stride over the units (group-major order kept); the
   // next unit's dependent loads -- column id, B column range, B rows, A run
   // bounds -- are issued one per stage of the current unit (hook 1 after its
@@ -1319,7 +1257,7 @@ __global__ __launch_bounds__(BIG_BS) CBG_SYM_WPE_ATTR void k_sym_panel(SymPanelA
 }
 
 // the deferred group units, panel by panel (their pairs as in k_sym_panel<false>)
-__global__ __launch_bounds__(BIG_BS) CBG_SYM_WPE_ATTR void k_sym_deferred(SymPanelArgs a) {
+__global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) void k_sym_deferred(SymPanelArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const SymPanelLds L = sym_lds(smem, a.hwords);
   const int n = *a.defer_n;
@@ -1641,22 +1579,12 @@ __device__ __forceinline__ void seg_scan_step(int key, double& val) {
 // __shfl_up pairs (ds_bpermute).
 template <int SR>
 __device__ __forceinline__ double wave_seg_scan_sorted(int key, double val) {
-#if CBG_XOR_DPP
   seg_scan_step<SR, 0x111, 0xf>(key, val);
   seg_scan_step<SR, 0x112, 0xf>(key, val);
   seg_scan_step<SR, 0x114, 0xf>(key, val);
   seg_scan_step<SR, 0x118, 0xf>(key, val);
   seg_scan_step<SR, 0x142, 0xa>(key, val);  // row_bcast:15 -> rows 1, 3
   seg_scan_step<SR, 0x143, 0xc>(key, val);  // row_bcast:31 -> rows 2, 3
-#else
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const int ok = __shfl_up(key, d);
-    const double ov = __shfl_up(val, d);
-    if (lane >= d && ok == key) val = Sem<SR>::add(ov, val);
-  }
-#endif
   return val;
 }
 __device__ __forceinline__ double readlane_f64(double v, int l) {
@@ -1795,11 +1723,7 @@ __global__ __launch_bounds__(256) void k_esc_wave(const int32_t* __restrict__ pe
   int cj[NPL];
 #pragma unroll
   for (int j = 0; j < NPL; ++j) {
-#if CBG_XOR_DPP
     int nk = __builtin_amdgcn_update_dpp(EMPTY_KEY, key[j], 0x130, 0xf, 0xf, false);  // wave_shl:1
-#else
-    int nk = __shfl_down(key[j], 1);
-#endif
     if (j + 1 < NPL) {
       const int f = __builtin_amdgcn_readlane(key[j + 1 < NPL ? j + 1 : j], 0);
       if (lane == WAVE - 1) nk = f;
@@ -1878,7 +1802,7 @@ __global__ __launch_bounds__(256) void k_copy_fused(int64_t nz, const int64_t* _
   }
 }
 
-// single-entry columns of <= big flops (k_classify copy1): C(:,j) = A(:,k) * b, flattened per
+// single-entry columns of <= big flops (k_classify): C(:,j) = A(:,k) * b, flattened per
 // wave along C like k_copy_fused (rows are A's, already ascending)
 template <int SR>
 __global__ __launch_bounds__(256) void k_copy_single(int64_t nz, const int64_t* __restrict__ cpB,
@@ -1925,7 +1849,7 @@ __global__ __launch_bounds__(256) void k_copy_single(int64_t nz, const int64_t* 
   }
 }
 
-// the single-entry columns of more than `big` flops (copy1 = 2): their sizes
+// the single-entry columns of more than `big` flops: their sizes
 // (flops = the A column's length) for an exclusive scan, so that the copy can be
 // split into equal chunks.  A block per column (round 4) left a hub column of
 // ~10^5 entries to 256 threads: at scale 24 that kernel ran 80 ms per phase
@@ -1991,24 +1915,12 @@ __global__ __launch_bounds__(256) void k_copy_single_big(int64_t nz, const int64
 // into the LDS value slot of its rank.  No hashing, no sort, coalesced output.
 // Two launch classes by slab size so that small slabs run 2 workgroups per CU
 // (their phases overlap) while large ones get the full LDS for values.
-#ifndef CBG_VEC_INIT  // slab LDS initialisation with 16-byte stores
-#define CBG_VEC_INIT 1
-#endif
-#ifndef CBG_ROWS_DIRECT  // bitmap slabs store C's rows from the bitmap words directly
-#define CBG_ROWS_DIRECT 1
-#endif
-#ifndef CBG_ROWS_DIRECT_NT  // ... as nontemporal stores: +66 GB of partial-line writes per scale-22 step
-#define CBG_ROWS_DIRECT_NT 0
-#endif
 // the rank-ordered row copies of the bitmap, rank and group rank slabs under IACC
 // as nontemporal stores like their values: whole lines, coalesced, unlike the
-// bitmap walk's partial lines above (scale 22: 312.0 -> 306.8 ms, three rounds each)
-#ifndef CBG_ROWS_NT
-#define CBG_ROWS_NT 1
-#endif
+// bitmap walk's partial lines (scale 22: 312.0 -> 306.8 ms, three rounds each)
 template <bool IA, class T>
 __device__ __forceinline__ void st_rows(T* p, T v) {
-  if constexpr (IA && CBG_ROWS_NT) st_emit(p, v);
+  if constexpr (IA) st_emit(p, v);
   else *p = v;
 }
 template <int CAP, int BS>
@@ -2185,12 +2097,10 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       const int id = SemI<SR>::identity();
       int4* v4 = reinterpret_cast<int4*>(vals);
       for (int j = tid; j < (nout + 3) >> 2; j += BS) v4[j] = make_int4(id, id, id, id);
-    } else if (CBG_VEC_INIT) {  // 16-byte LDS stores (CAP is even, vals is 16-byte aligned)
+    } else {  // 16-byte LDS stores (CAP is even, vals is 16-byte aligned): flat to +0.3 % at 22, +2.5 % at 18
       const double id = Sem<SR>::identity();
       double2* v2 = reinterpret_cast<double2*>(vals);
       for (int j = tid; j < (nout + 1) >> 1; j += BS) v2[j] = make_double2(id, id);
-    } else {
-      for (int j = tid; j < nout; j += BS) vals[j] = Sem<SR>::identity();
     }
     int total = 0;
     if (pre) {
@@ -2300,8 +2210,6 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       }
     }
     if (has_next) fetch_stage2(nrec);
-    // values: coalesced copy; rows: each word scatters its set bits to their
-    // ranks in LDS (reusing the value array), then a coalesced copy
     if (IA && !(c_dbg & 8)) {
       // rows and values in rank order (C's order): coalesced copies
       const int* ivals = reinterpret_cast<const int*>(vals);
@@ -2309,39 +2217,22 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         st_rows<true>(&out_ir[obase + j], ivals[CAP + j]);
         st_stream(&out_val[obase + j], (double)ivals[j]);
       }
-    } else if (!(c_dbg & 8) && CBG_ROWS_DIRECT) {
+    } else if (!(c_dbg & 8)) {
       // rows straight from the bitmap words to C (a wave's lanes hold
       // consecutive words, so their ranks -- the store addresses -- are
-      // consecutive too): no LDS staging of the rows, no barriers
+      // consecutive too): no LDS staging of the rows, no barriers.  Plain
+      // stores, whose partial lines L2 merges: nontemporal ones wrote +66 GB
+      // of partial lines per scale-22 step
       for (int w = tid; w < words; w += BS) {
         unsigned x = bm[w];
         int pos = wpre[w];
         while (x) {
-#if CBG_ROWS_DIRECT_NT
-          st_stream(&out_ir[obase + pos++], lo + w * 32 + __ffs(x) - 1);
-#else
-          out_ir[obase + pos++] = lo + w * 32 + __ffs(x) - 1;  // L2 merges the partial lines
-#endif
+          out_ir[obase + pos++] = lo + w * 32 + __ffs(x) - 1;
           x &= x - 1;
         }
       }
       for (int j = tid; j < nout; j += BS)
         st_stream(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
-    } else if (!(c_dbg & 8)) {
-      for (int j = tid; j < nout; j += BS)
-        st_stream(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
-      __syncthreads();
-      int* rows = reinterpret_cast<int*>(vals);
-      for (int w = tid; w < words; w += BS) {
-        unsigned x = bm[w];
-        int pos = wpre[w];
-        while (x) {
-          rows[pos++] = lo + w * 32 + __ffs(x) - 1;
-          x &= x - 1;
-        }
-      }
-      __syncthreads();
-      for (int j = tid; j < nout; j += BS) st_stream(&out_ir[obase + j], rows[j]);
     }
     __syncthreads();  // LDS is refilled by the next slab
     phase_mark(tmark, 6);
@@ -2467,17 +2358,8 @@ __device__ __forceinline__ void block_products_sid(int total, const unsigned sho
 
 // numeric of a sparse (column, panel) pair (hash-mode slab, <= SPARSE_SLAB_MAX
 // products): LDS hash sized to the pair's nnz, sorted emit by row buckets
-#ifndef CBG_EMIT_MOFF  // emit ranks from cached in-bucket row offsets (1 LDS read per bucket member)
-#define CBG_EMIT_MOFF 1
-#endif
-#ifndef CBG_EMIT_REG  // hash_emit_reg: slots held in registers across the emit's passes
-#define CBG_EMIT_REG 1
-#endif
 #ifndef CBG_EMIT_NB_DIV  // emit buckets of a hash slab: power of two <= T / DIV
 #define CBG_EMIT_NB_DIV 4
-#endif
-#ifndef CBG_HASH_MEMB_ALIAS  // emit member list in the idle staging arrays (3072-slot slabs: 3 blocks per CU, not 2)
-#define CBG_HASH_MEMB_ALIAS 0  // 1: +0.4 % at 22, -0.7 % at 18 (same box, 2 runs): within noise, off
 #endif
 template <int T_, int BS>
 struct SlabHashLds {
@@ -2487,23 +2369,14 @@ struct SlabHashLds {
   static constexpr int MEMB = (T * CBG_HASH_LOAD_DEN + CBG_HASH_LOAD_NUM - 1) / CBG_HASH_LOAD_NUM;  // max nnz
   // vals[T] f64 | keys[T] | bv[BS] f64 | pref[BS+4] | st[BS] | tmp | boff[NB+4] | cur[NB] | members[MEMB] u16
   // bv|pref|st: idle during the emit, which reuses them for its in-bucket row
-  // offsets (u16, MOFF) and, where both fit, its member list
+  // offsets (u16; the member list keeps its own array: placed there too, 3
+  // blocks per CU instead of 2 for the 3072-slot slabs were within noise)
   static constexpr int PBYTES = BS * 8 + (BS + 4) * 4 + BS * 4;  // staging region bv | pref | st
-  static constexpr int IDLE = PBYTES;
-  static constexpr bool MOFF_FITS = MEMB * 2 <= IDLE;
-  static constexpr bool MEMB_ALIAS = CBG_HASH_MEMB_ALIAS && 2 * MEMB * 2 <= IDLE;
+  static constexpr bool MOFF_FITS = MEMB * 2 <= PBYTES;
   static constexpr int TMP_OFF = T * 12 + PBYTES;
-  static constexpr int BYTES = TMP_OFF + (BS / WAVE + 4) * 4 + (2 * NB + 4) * 4 + (MEMB_ALIAS ? 0 : MEMB * 2);
+  static constexpr int BYTES = TMP_OFF + (BS / WAVE + 4) * 4 + (2 * NB + 4) * 4 + MEMB * 2;
 };
 
-#ifndef CBG_HASH_WPE  // waves per SIMD the hash-slab kernels are compiled for (0: the compiler's choice)
-#define CBG_HASH_WPE 0
-#endif
-#if CBG_HASH_WPE > 0
-#define CBG_HASH_WPE_ATTR __attribute__((amdgpu_waves_per_eu(CBG_HASH_WPE)))
-#else
-#define CBG_HASH_WPE_ATTR
-#endif
 // CMLEN: cmapP entries are (start, len) -- the whole-column map of the
 // column bins -- instead of the panel maps' (first, end)
 // INL (with CMLEN): A's columns as inline records (k_inline_cols): an entry of
@@ -2511,7 +2384,7 @@ struct SlabHashLds {
 // record (no map hop, no gathers of A, no staging); the longer ones are staged
 // as usual, and a chunk without any skips the scan
 template <int SR, int TT, int BS, bool CMLEN, typename VA = double, bool INL = false>
-__global__ __launch_bounds__(BS) CBG_HASH_WPE_ATTR void k_num_slab_hash(const SlabRec* __restrict__ list, int n, int* __restrict__ queue,
+__global__ __launch_bounds__(BS) void k_num_slab_hash(const SlabRec* __restrict__ list, int n, int* __restrict__ queue,
                                                       int plog, const int32_t* __restrict__ irB,
                                                       const double* __restrict__ valB, PMap pm,
                                                       const int32_t* __restrict__ irA,
@@ -2538,8 +2411,7 @@ __global__ __launch_bounds__(BS) CBG_HASH_WPE_ATTR void k_num_slab_hash(const Sl
   int* tmp = reinterpret_cast<int*>(smem + L::TMP_OFF);
   int* boff = tmp + BS / WAVE + 4;
   int* cur = boff + NB + 4;
-  unsigned short* members = L::MEMB_ALIAS ? reinterpret_cast<unsigned short*>(bv) + L::MEMB
-                                          : reinterpret_cast<unsigned short*>(cur + NB);
+  unsigned short* members = reinterpret_cast<unsigned short*>(cur + NB);
   const int tid = threadIdx.x;
   int i = blockIdx.x;
   if (i >= n) return;
@@ -2586,17 +2458,12 @@ __global__ __launch_bounds__(BS) CBG_HASH_WPE_ATTR void k_num_slab_hash(const Sl
     }
     const bool pre = staged(rec);
     unsigned long long tmark = wall_clock64();
-    if (CBG_VEC_INIT) {  // 16-byte LDS stores (T is a multiple of 256; vals and keys are 16-byte aligned)
+    {  // 16-byte LDS stores (T is a multiple of 256; vals and keys are 16-byte aligned)
       const double id = Sem<SR>::identity();
       double2* v2 = reinterpret_cast<double2*>(vals);
       int4* k4 = reinterpret_cast<int4*>(keys);
       for (int j = tid; j < T / 2; j += BS) v2[j] = make_double2(id, id);
       for (int j = tid; j < T / 4; j += BS) k4[j] = make_int4(EMPTY_KEY, EMPTY_KEY, EMPTY_KEY, EMPTY_KEY);
-    } else {
-      for (int j = tid; j < T; j += BS) {
-        keys[j] = EMPTY_KEY;
-        vals[j] = Sem<SR>::identity();
-      }
     }
     __syncthreads();
     phase_mark(tmark, 7);
@@ -2668,18 +2535,13 @@ __global__ __launch_bounds__(BS) CBG_HASH_WPE_ATTR void k_num_slab_hash(const Sl
     const int bshift = sl > LOGNB ? sl - LOGNB : 0;
     // in-bucket offsets fit u16 for panel-group slabs (span <= 2^(plog+4) rows,
     // bshift <= 15, 17 for groups of 64 panels); every slab uses them while bshift <= 16
-    constexpr bool MOFF = L::MOFF_FITS && CBG_EMIT_MOFF;
     if (c_dbg & 1024)
       ;
-    else if (MOFF && CBG_EMIT_REG && bshift <= 16)
+    else if (L::MOFF_FITS && bshift <= 16)
       hash_emit_reg<T, BS, NB>(keys, vals, rec.lo, bshift, boff, cur, members, tmp,
                                reinterpret_cast<unsigned short*>(bv), out_ir, out_val, rec.obase);
-    else if (MOFF && bshift <= 16)
-      hash_emit_sorted<T, BS, NB, MOFF>(keys, vals, rec.lo, bshift, boff, cur, members, tmp, out_ir, out_val,
-                                        rec.obase, reinterpret_cast<unsigned short*>(bv));
     else
-      hash_emit_sorted<T, BS, NB, false>(keys, vals, rec.lo, bshift, boff, cur, members, tmp, out_ir, out_val,
-                                         rec.obase);
+      hash_emit_sorted<T, BS, NB>(keys, vals, rec.lo, bshift, boff, cur, members, tmp, out_ir, out_val, rec.obase);
     __syncthreads();  // LDS is reset for the next slab
     phase_mark(tmark, 15);
     if (!has_next) break;
@@ -3193,7 +3055,6 @@ __global__ void k_col_scatter(int64_t n, const int32_t* __restrict__ cnt, const 
 // ----------------------------------------------------------------------------
 void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_tile& C, hipStream_t s, LocalStats* st,
                        OutSink* sink, bool sym_only = false);
-static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 // Device properties and occupancy are cached per (device, kernel, block size,
 // LDS bytes): a process may drive several GPUs from several threads (one
@@ -3242,22 +3103,14 @@ int& comm_reserve_cus() {
 }
 static int active_cus() { return std::max(1, device_cus() - comm_reserve_cus()); }
 
-template <class K>
-static void set_lds(K kernel, size_t bytes) {
-  if (bytes > 65536) CBG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
 // bins of the symbolic phase (key = flops)
 //  0: F == 0 | 1: <=32 wave T64 | 2: <=128 wave T256 | 3: <=512 wave T1024 |
 //  4: <=1024 block T2048 | 5: <=2048 block T4096 | 6: <=4096 block T8192 | 7: big
 // symbolic bins: 1-9 (flops <= 2 ... 512) expand-sort-compress waves of 32 ... 1
-// columns (symbolic and numeric in one pass; CBG_SYM_FUSED_LAST = 8 leaves bin 9
-// to the wave hash), 10-12 block hash
-#ifndef CBG_SYM_FUSED_LAST
-#define CBG_SYM_FUSED_LAST 9
-#endif
+// columns (symbolic and numeric in one pass: the fused bins 1..SYM_FUSED_LAST),
+// 10-12 block hash
 static constexpr int64_t kSymThr[] = {0, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096};
-constexpr int SYM_FUSED_LAST = CBG_SYM_FUSED_LAST;
+constexpr int SYM_FUSED_LAST = 9;
 // columns with more flops than this take the bitmap+rank slab path (runtime
 // override: CBG_BIG_FLOPS); it must stay <= 4096 so that every other column's
 // nnz fits the largest numeric hash bin
@@ -3292,14 +3145,28 @@ static_assert(kSymThr[LOW_CUT_BIN0 - 1] == LOW_CUT_FLOPS && kSymThr[LOW_CUT_BIN1
 //  5: <=512 block T1024 | 6: <=1024 block T2048 | 7: <=2048 block T4096 | 8: <=4096 block T8192 | 9: big
 static const int64_t kNumThr[] = {0, 32, 64, 128, 256, 512, 1024, 2048, 4096};
 
-template <int LOGT>
-static void launch_sym_wave(const int32_t* perm, int n, const cbg_tile& B, const int2* cmap, const cbg_tile& A,
-                            int32_t* cnt, hipStream_t s) {
-  if (n <= 0) return;
-  const size_t lds = 4 * SymWaveLds<LOGT>::INTS * sizeof(int);
-  set_lds(k_sym_wave<LOGT>, lds);
-  hipLaunchKernelGGL(k_sym_wave<LOGT>, dim3(nblk(n, 4)), dim3(256), lds, s, perm, n, B.cp, B.ir, cmap, A.ir, cnt);
+// f(tag) with the runtime semiring as a compile-time tag: decltype(tag)::value is the kernels' SR
+template <class F>
+static void with_semiring(int semiring, F&& f) {
+  if (semiring == CBG_MIN_PLUS) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
 }
+
+// One queue-driven (persistent) slab kernel over list[0, n), n > 0: a fresh
+// queue counter, the kernel's LDS size, a grid of the blocks resident on the
+// active CUs (at most one per slab); `tail` follows (list, n, queue) in the
+// kernel's arguments.  The counter lives until the multiply's last sync (df).
+template <class K, class... Tail>
+static void launch_queued(K k, int bs, size_t lds, const SlabRec* list, int n, hipStream_t s, DeferredFree& df,
+                          Tail... tail) {
+  DBuf<int> queue(1);
+  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
+  set_lds(k, lds);
+  const int grid = (int)std::min<int64_t>(n, (int64_t)blocks_per_cu(k, bs, lds) * active_cus());
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(bs), lds, s, list, n, queue.p, tail...);
+  df.take(queue);
+}
+
 // expand-sort-compress bin b (flops <= fmax = 64 >> (b - 1)... as CPW = 64 / fmax
 // columns per wave; one column per wave when A's rows leave no room for the
 // column bits of the sort key)
@@ -3401,16 +3268,10 @@ static void launch_num_block_hash(const int32_t* perm, int n, const cbg_tile& B,
   constexpr int L = SlabHashLds<1 << LOGT, BS>::BYTES;
   int lm = 0;
   while ((1LL << lm) < A.m) ++lm;  // emit buckets span [0, 2^lm)
-  DBuf<int> queue(1);
-  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
+  // (every resident block: a quarter / a 16th of them, leaving the big-column
+  // slabs on the main stream more CUs, were 424 / 537 vs 418.5 ms at scale 22)
   auto go = [&](auto k, const auto* valA) {
-    set_lds(k, L);
-    const int per_cu = blocks_per_cu(k, BS, L);
-    // (a quarter / a 16th of the resident blocks, leaving the big-column slabs on
-    // the main stream more CUs: 424 / 537 vs 418.5 ms at scale 22)
-    const int grid = (int)std::min<int64_t>(n, (int64_t)per_cu * active_cus());
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(BS), L, s, rec.p, n, queue.p, lm, B.ir, B.val, PMap{cmap, 0, 1},
-                       A.ir, valA, C.ir, C.val, ainl);
+    launch_queued(k, BS, L, rec.p, n, s, df, lm, B.ir, B.val, PMap{cmap, 0, 1}, A.ir, valA, C.ir, C.val, ainl);
   };
   // A's f32 values (exact, see k_vals_f32) when the big-column path made them;
   // A's columns as inline records when the small-column passes have them
@@ -3418,7 +3279,6 @@ static void launch_num_block_hash(const int32_t* perm, int n, const cbg_tile& B,
   else if (valAf) go(k_num_slab_hash<SR, 1 << LOGT, BS, true, float>, valAf);
   else go(k_num_slab_hash<SR, 1 << LOGT, BS, true, double>, A.val);
   df.take(rec);
-  df.take(queue);
 }
 
 struct BigPlan {
@@ -3448,72 +3308,49 @@ template <int SR, int T, int BS>
 static void launch_slab_hash(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                              const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  constexpr int L = SlabHashLds<T, BS>::BYTES;
-  DBuf<int> queue(1);
-  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
   auto go = [&](auto k, const auto* valA) {
-    set_lds(k, L);
-    const int per_cu = blocks_per_cu(k, BS, L);
-    const int grid = (int)std::min<int64_t>(n, (int64_t)per_cu * active_cus());
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(BS), L, s, list, n, queue.p, bp.plog, B.ir, B.val, bp.pm(),
-                       A.ir, valA, C.ir, C.val, (const int4*)nullptr);
+    launch_queued(k, BS, SlabHashLds<T, BS>::BYTES, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
+                  C.val, (const int4*)nullptr);
   };
   // (A's exact f32 values come as (row, f32) records whenever they exist; f64
   // values as (row, f64) records when they were worth packing, see k_pack_rvd)
   if (bp.valAp) go(k_num_slab_hash<SR, T, BS, false, PackedRV>, bp.valAp);
   else if (bp.valAd) go(k_num_slab_hash<SR, T, BS, false, PackedRVD>, bp.valAd);
   else go(k_num_slab_hash<SR, T, BS, false, double>, A.val);
-  df.take(queue);
 }
 
 template <int SR, int CAP, int BS>
 static void launch_slab_bitmap(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                                const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  constexpr int L = SlabLds<CAP, BS>::BYTES;
-  DBuf<int> queue(1);
-  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
   auto go = [&](auto k, const auto* valA) {
-    set_lds(k, L);
-    const int per_cu = blocks_per_cu(k, BS, L);
-    const int grid = (int)std::min<int64_t>(n, (int64_t)per_cu * active_cus());
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(BS), L, s, list, n, queue.p, bp.plog, B.ir, B.val, bp.pm(),
-                       A.ir, valA, C.ir, C.val, bp.gbm.p, bp.cuts.p);
+    launch_queued(k, BS, SlabLds<CAP, BS>::BYTES, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
+                  C.val, bp.gbm.p, bp.cuts.p);
   };
   // (IACC only with the packed records: integers of magnitude <= 2^24 are f32-exact)
-  if (bp.all_kept) {
-    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, true, true>, bp.valAp);
-    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, true, false>, bp.valAp);
-    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, true, false>, bp.valAd);
-    else go(k_num_slab<SR, CAP, BS, double, true, false>, A.val);
-  } else {
-    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, false, true>, bp.valAp);
-    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, false, false>, bp.valAp);
-    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, false, false>, bp.valAd);
-    else go(k_num_slab<SR, CAP, BS, double, false, false>, A.val);
-  }
-  df.take(queue);
+  auto pick = [&](auto kept) {
+    constexpr bool KEPT = decltype(kept)::value;
+    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, true>, bp.valAp);
+    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, false>, bp.valAp);
+    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, KEPT, false>, bp.valAd);
+    else go(k_num_slab<SR, CAP, BS, double, KEPT, false>, A.val);
+  };
+  if (bp.all_kept) pick(std::true_type{});
+  else pick(std::false_type{});
 }
 
 template <int SR, int NCAP>
 static void launch_slab_rank(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                              const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  DBuf<int> queue(1);
-  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
+  const int L = bp.iacc ? SlabRankLds<NCAP, RANK_BS, 4>::BYTES : SlabRankLds<NCAP, RANK_BS, 8>::BYTES;
   auto go = [&](auto k, const auto* valA) {
-    const int L = bp.iacc ? SlabRankLds<NCAP, RANK_BS, 4>::BYTES : SlabRankLds<NCAP, RANK_BS, 8>::BYTES;
-    set_lds(k, L);
-    const int per_cu = blocks_per_cu(k, RANK_BS, L);
-    const int grid = (int)std::min<int64_t>(n, (int64_t)per_cu * active_cus());
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(RANK_BS), L, s, list, n, queue.p, B.ir, B.val, bp.pm(),
-                       A.ir, valA, C.ir, C.val);
+    launch_queued(k, RANK_BS, L, list, n, s, df, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val);
   };
   if (bp.iacc) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRV, true>, bp.valAp);
   else if (bp.valAp) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRV, false>, bp.valAp);
   else if (bp.valAd) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRVD, false>, bp.valAd);
   else go(k_num_slab_rank<SR, NCAP, RANK_BS, double, false>, A.val);
-  df.take(queue);
 }
 
 // hash-mode single-panel slabs of more than this many nonzeros run as rank
@@ -3526,29 +3363,21 @@ template <int SR, int NCAP, int SPANLOG = GRANK_SPAN_LOG, int PMAX = GRANK_PMAX>
 static void launch_slab_grank(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                               const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  DBuf<int> queue(1);
-  CBG_HIP(hipMemsetAsync(queue.p, 0, sizeof(int), s));
+  const int L = bp.iacc ? SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 4>::BYTES
+                        : SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 8>::BYTES;
   auto go = [&](auto k, const auto* valA) {
-    const int L = bp.iacc ? SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 4>::BYTES
-                          : SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 8>::BYTES;
-    set_lds(k, L);
-    const int per_cu = blocks_per_cu(k, RANK_BS, L);
-    const int grid = (int)std::min<int64_t>(n, (int64_t)per_cu * active_cus());
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(RANK_BS), L, s, list, n, queue.p, bp.plog, B.ir, B.val, bp.pm(),
-                       A.ir, valA, C.ir, C.val);
+    launch_queued(k, RANK_BS, L, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val);
   };
   if (bp.iacc) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRV, true>, bp.valAp);
   else if (bp.valAp) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRV, false>, bp.valAp);
   else if (bp.valAd) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRVD, false>, bp.valAd);
   else go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, double, false>, A.val);
-  df.take(queue);
 }
 
 // ncls[c] slabs of class c, stored consecutively in `list` (k_slab_fill)
-
 template <int SR>
 static void launch_slabs(const SlabRec* list, const int* ncls, const BigPlan& bp, const cbg_tile& A,
-                         const cbg_tile& B, cbg_tile& C, hipStream_t s, hipStream_t side, DeferredFree& df) {
+                         const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   const SlabRec* at[SLAB_NCLS];
   int64_t o = 0;
   for (int c = 0; c < SLAB_NCLS; ++c) {
@@ -3557,19 +3386,18 @@ static void launch_slabs(const SlabRec* list, const int* ncls, const BigPlan& bp
   }
   // (hash classes queued behind the small-column bins on the side stream were
   // 3-4 % slower at scale 22: every slab class runs on the main stream)
-  auto hs = [&](int) { return s; };
   launch_slab_bitmap<SR, SLAB_SMALL_CAP, SLAB_SMALL_BS>(at[0], ncls[0], bp, A, B, C, s, df);
   launch_slab_bitmap<SR, SLAB_LARGE_CAP, SLAB_LARGE_BS>(at[1], ncls[1], bp, A, B, C, s, df);
   static_assert(SLAB_HASH_NCLS == 9, "hash slab classes (CBG_HASH_TABLES)");
-  launch_slab_hash<SR, 512, 256>(at[2], ncls[2], bp, A, B, C, hs(0), df);
-  launch_slab_hash<SR, 768, 256>(at[3], ncls[3], bp, A, B, C, hs(1), df);
-  launch_slab_hash<SR, 1024, 256>(at[4], ncls[4], bp, A, B, C, hs(2), df);
-  launch_slab_hash<SR, 1536, 256>(at[5], ncls[5], bp, A, B, C, hs(3), df);
-  launch_slab_hash<SR, 2048, 256>(at[6], ncls[6], bp, A, B, C, hs(4), df);
-  launch_slab_hash<SR, 3072, 512>(at[7], ncls[7], bp, A, B, C, hs(5), df);
-  launch_slab_hash<SR, 4096, 512>(at[8], ncls[8], bp, A, B, C, hs(6), df);
-  launch_slab_hash<SR, 6144, 512>(at[9], ncls[9], bp, A, B, C, hs(7), df);
-  launch_slab_hash<SR, 8192, 512>(at[10], ncls[10], bp, A, B, C, hs(8), df);
+  launch_slab_hash<SR, 512, 256>(at[2], ncls[2], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 768, 256>(at[3], ncls[3], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 1024, 256>(at[4], ncls[4], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 1536, 256>(at[5], ncls[5], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 2048, 256>(at[6], ncls[6], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 3072, 512>(at[7], ncls[7], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 4096, 512>(at[8], ncls[8], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 6144, 512>(at[9], ncls[9], bp, A, B, C, s, df);
+  launch_slab_hash<SR, 8192, 512>(at[10], ncls[10], bp, A, B, C, s, df);
   // (class order: rank and group rank slabs first, or between the two bitmap
   // classes: 347.5 / 346.2 vs 343.5 ms at scale 22)
   // (the single-panel rank slabs by the two-level rank of the group slabs, 1
@@ -3580,9 +3408,7 @@ static void launch_slabs(const SlabRec* list, const int* ncls, const BigPlan& bp
   launch_slab_rank<SR, 1024>(at[SLAB_RANK0], ncls[SLAB_RANK0], bp, A, B, C, s, df);
   launch_slab_grank<SR, 4096>(at[SLAB_GRANK0 + 1], ncls[SLAB_GRANK0 + 1], bp, A, B, C, s, df);
   launch_slab_grank<SR, 2048>(at[SLAB_GRANK0], ncls[SLAB_GRANK0], bp, A, B, C, s, df);
-
 }
-
 
 // kept symbolic bitmaps (32 KiB per (column, panel) pair): CBG_BITMAP_BUDGET_GB,
 // default 48 GB (scale 22 on one GPU: 16 GB -> 32 GB was +3.7 %), never more
@@ -3651,7 +3477,7 @@ constexpr int BIN_HIST_INTS = 4 * MAXBINS + 4 + 8;  // counts | offsets | big, t
 static void bin_classify(int64_t n, const int64_t* flops, int32_t* cnt, int mode, const int64_t* thr,
                          int nthr, int64_t big, BinPending& bp, hipStream_t s, int64_t fused_max = 0,
                          const int64_t* cpB = nullptr, int big_bin = MAXBINS, int thin_R = 0, int thin_bin = 0,
-                         int copy1 = 0, int64_t low = 0) {
+                         int64_t low = 0) {
   bp.bt.nb = nthr + 1;
   for (int i = 0; i < nthr; ++i) bp.bt.t[i] = thr[i];
   bp.bin.reset(n);
@@ -3660,7 +3486,7 @@ static void bin_classify(int64_t n, const int64_t* flops, int32_t* cnt, int mode
   CBG_HIP(hipMemsetAsync(bp.hist.p, 0, sizeof(int) * BIN_HIST_INTS, s));
   unsigned long long* be = (cpB && mode == 0) ? reinterpret_cast<unsigned long long*>(bp.hist.p + 2 * MAXBINS) : nullptr;
   unsigned long long* bf = reinterpret_cast<unsigned long long*>(bp.hist.p + 2 * MAXBINS + 4);
-  hipLaunchKernelGGL(k_classify, dim3(nblk(n, 256 * BIN_ITEMS)), dim3(256), 0, s, n, flops, cnt, mode, copy1, big, bp.bt,
+  hipLaunchKernelGGL(k_classify, dim3(nblk(n, 256 * BIN_ITEMS)), dim3(256), 0, s, n, flops, cnt, mode, big, bp.bt,
                      bp.bin.p, bp.hist.p, fused_max, cpB, big_bin, be, bf, thin_R, thin_bin, be ? low : 0, bf + MAXBINS);
   // one copy of counts | offsets | big entries | flops per bin | lo_stats
   bp.host = host_stage(mode == 0 ? STAGE_BINS_SYM : STAGE_BINS_NUM);
@@ -3755,6 +3581,28 @@ struct APrep {
   DBuf<PackedRV> valp;  // (row, f32) records (af == 1)
   DBuf<PackedRVD> valpd;  // (row, f64) records (af == 0)
   int af = -1;       // -1 not checked yet, 0 some value is not an exact f32, 1 valf holds A's values
+  bool holds(const cbg_tile& A, uint64_t sir, uint64_t scp) const {
+    return active && ir == A.ir && cp == A.cp && ser_ir == sir && ser_cp == scp && nnz == A.nnz && nzc == A.nzc &&
+           m == A.m && n == A.n;
+  }
+  // drop what was built for the previous A; the maps of A (none: nullptr) come next
+  void rebind(const cbg_tile* A, uint64_t sir, uint64_t scp) {
+    cmap.release();
+    clen8.release();
+    cmapP.release();
+    valf.release();
+    valp.release();
+    valpd.release();
+    af = ai = plog = -1;
+    ir = A ? A->ir : nullptr;
+    cp = A ? A->cp : nullptr;
+    ser_ir = sir;
+    ser_cp = scp;
+    nnz = A ? A->nnz : -1;
+    nzc = A ? A->nzc : -1;
+    m = A ? A->m : -1;
+    n = A ? A->n : -1;
+  }
 };
 
 // A's values narrowed to f32, and whether every one survives the round trip
@@ -3929,20 +3777,8 @@ static APrep& aprep() {
 }
 void aprep_begin() { aprep().active = true; }
 void aprep_end() {
-  APrep& a = aprep();
-  a.cmap.release();
-  a.clen8.release();
-  a.cmapP.release();
-  a.valf.release();
-  a.valp.release();
-  a.valpd.release();
-  a.af = -1;
-  a.ai = -1;
-  a.active = false;
-  a.ir = a.cp = nullptr;
-  a.ser_ir = a.ser_cp = 0;
-  a.nnz = a.nzc = a.m = a.n = -1;
-  a.plog = -1;
+  aprep().rebind(nullptr, 0, 0);
+  aprep().active = false;
 }
 
 LocalStats& thread_stats() {
@@ -3978,6 +3814,808 @@ void local_symbolic(const cbg_tile& A, const cbg_tile& B, hipStream_t s, int64_t
   if (nnz) *nnz = st.nnz;
 }
 
+// CBG_DBG (the ablation mask at the top of this file), read once per process
+static int dbg_mask() {
+  static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
+  return dbg;
+}
+
+// The calling thread's side stream for the small-column bins (independent of
+// the big columns), its copy stream for the numeric's direct copies into C, and
+// the timing events: created once per thread and reused by every multiply.
+// The small-column bins of the symbolic and the numeric run on the side stream
+// (serialized on the main one: -0.5 % at scale 22, -5 % at 18), the symbolic's
+// on the main one where the big columns dominate (sym_small_columns)
+struct LocalStreams {
+  hipStream_t side = nullptr, scopy = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cjoin = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+  static LocalStreams& mine() {
+    static thread_local LocalStreams t;
+    if (!t.side) {
+      CBG_HIP(hipStreamCreateWithFlags(&t.side, hipStreamNonBlocking));
+      CBG_HIP(hipStreamCreateWithFlags(&t.scopy, hipStreamNonBlocking));
+      CBG_HIP(hipEventCreateWithFlags(&t.ev_fork, hipEventDisableTiming));
+      CBG_HIP(hipEventCreateWithFlags(&t.ev_join, hipEventDisableTiming));
+      CBG_HIP(hipEventCreateWithFlags(&t.ev_cjoin, hipEventDisableTiming));
+    }
+    if (!t.ev0) {
+      CBG_HIP(hipEventCreate(&t.ev0));
+      CBG_HIP(hipEventCreate(&t.ev1));
+      CBG_HIP(hipEventCreate(&t.ev2));
+    }
+    return t;
+  }
+  void fork(hipStream_t main) const {
+    CBG_HIP(hipEventRecord(ev_fork, main));
+    CBG_HIP(hipStreamWaitEvent(side, ev_fork, 0));
+  }
+  void join(hipStream_t main) const {
+    CBG_HIP(hipEventRecord(ev_join, side));
+    CBG_HIP(hipStreamWaitEvent(main, ev_join, 0));
+  }
+  void join_copy(hipStream_t main) const {
+    CBG_HIP(hipEventRecord(ev_cjoin, scopy));
+    CBG_HIP(hipStreamWaitEvent(main, ev_cjoin, 0));
+  }
+};
+
+// symbolic bins: kSymThr (clipped at `big`), then the big columns by panel
+// group size 2^GROUP_LOG_MAX .. 1 (columns with F * g / R <= GROUP_PRODUCTS
+// expected products per group; CBG_GROUPS=0 keeps every pair on its own), then
+// the thin ones
+constexpr int NSMALL = 13, NGCLS = GROUP_LOG_MAX + 1, THIN_BIN = NSMALL + NGCLS;
+static_assert(THIN_BIN < MAXBINS, "bins");
+
+// What one local multiply carries from stage to stage (local_spgemm_impl runs
+// the stages in order).  Every device buffer here lives until the multiply
+// returns, like the kernels that read it; Cg and df come first, so they are
+// destroyed last (df waits for the streams on an error path).
+struct LocalMul {
+  const cbg_tile& A;
+  const cbg_tile& B;
+  const int semiring;
+  cbg_tile& C;
+  const hipStream_t s;  // the caller's stream: the main one
+  OutSink* const sink;
+  const bool sym_only;
+  const int64_t nz;  // B's nonempty columns
+  LocalStreams& ts;
+  APrep& ap;
+  TileGuard Cg;  // C's arrays until the multiply has completed (exceptions included)
+  DeferredFree df;
+  int64_t work[CBG_WORK_N] = {};  // cbg_last_work_stats
+  // The device buffers, in the order the multiply makes them (they return to the
+  // pool in the reverse order, before df's).
+  // A's column map (reused across the phases of one MemEfficientSpGEMM: ap's, else these)
+  DBuf<int2> cmap_own;
+  DBuf<unsigned char> clen8_own;
+  DBuf<int2>& cmap() { return ap.active ? ap.cmap : cmap_own; }
+  DBuf<unsigned char>& clen8() { return ap.active ? ap.clen8 : clen8_own; }
+  // per B column: flops, nnz of C's column
+  DBuf<int64_t> flops;
+  DBuf<int32_t> cnt;
+  // the symbolic's bins and cut
+  Binned sb;
+  int64_t big = 0;  // columns of more flops are big (lowered where the rule takes the lower cut)
+  int thin_R = 0;   // > 0: thin columns are on (k_classify)
+  int64_t big_entries = 0, thin_entries = 0;  // B entries of the big / thin columns (read back with sync 1)
+  bool big_dominant = false;  // the (column, panel) units carry most of the flops over >= 8 row panels
+  BigPlan bp;
+  // small columns' symbolic and numeric in one pass (bins 1..SYM_FUSED_LAST) into
+  // temporary slots, and the thin columns' unique entries behind them
+  DBuf<int32_t> fused_ir;
+  DBuf<double> fused_val;
+  DBuf<int64_t> fused_slot;  // temporary slot of each fused column (-1: none)
+  size_t fused_off[SYM_FUSED_LAST + 2] = {};  // temporary slots of the fused bins 1..SYM_FUSED_LAST
+  // A's inline records, its values as f32 / (row, value) records (ap's, else these)
+  DBuf<int4> ainl;
+  DBuf<float> valf_own;
+  DBuf<PackedRV> valp_own;
+  DBuf<PackedRVD> valpd_own;
+  DBuf<float>& valf() { return ap.active ? ap.valf : valf_own; }
+  DBuf<PackedRV>& valp() { return ap.active ? ap.valp : valp_own; }
+  DBuf<PackedRVD>& valpd() { return ap.active ? ap.valpd : valpd_own; }
+  // A's verdicts (cached with the maps): f32-exact, integral, max |a|
+  int af = -1, ai = -1, amax = 0;
+  DBuf<int> af_flag, bint;
+  // [0] A not f32-exact | [1] A not integral, [2] max |a| | [4] B not integral,
+  // [5] max |b|, [6] B's largest column |sum| (IACC; read with sync 2)
+  int* afh = nullptr;
+  // after the symbolic: C's column pointers, the slab lists, the numeric's bins
+  DBuf<int64_t> colptr, sbase;
+  DBuf<SlabRec> slist;
+  BinPending npend;
+  DBuf<int64_t> flag, pos, sb_sz, sb_off;
+  int ncls[SLAB_NCLS] = {};
+  Binned nbn;
+  // read back with sync 2
+  int64_t nnzc = 0, nzcC = 0, flops_total = 0, nslabs = 0, single_big_entries = 0;
+
+  LocalMul(const cbg_tile& A_, const cbg_tile& B_, int semiring_, cbg_tile& C_, hipStream_t s_, OutSink* sink_,
+           bool sym_only_)
+      : A(A_), B(B_), semiring(semiring_), C(C_), s(s_), sink(sink_), sym_only(sym_only_), nz(B_.nzc),
+        ts(LocalStreams::mine()), ap(aprep()) {}
+};
+
+// Stage 1: A's column map, from the cache of this thread's MemEfficientSpGEMM
+// call when it holds this A
+static void prep_a_maps(LocalMul& m) {
+  const cbg_tile& A = m.A;
+  APrep& ap = m.ap;
+  const uint64_t ser_ir = ap.active ? pool().serial_of(A.ir) : 0, ser_cp = ap.active ? pool().serial_of(A.cp) : 0;
+  const bool a_hit = ap.holds(A, ser_ir, ser_cp);
+  if (ap.active && !a_hit) ap.rebind(&A, ser_ir, ser_cp);
+  if (!a_hit) {
+    DBuf<int2>& cmap = m.cmap();
+    DBuf<unsigned char>& clen8 = m.clen8();
+    cmap.reset(A.n + 1);
+    clen8.reset(A.n + 1);
+    CBG_HIP(hipMemsetAsync(cmap.p, 0, sizeof(int2) * (A.n + 1), m.s));
+    CBG_HIP(hipMemsetAsync(clen8.p, 0, A.n + 1, m.s));
+    hipLaunchKernelGGL(k_colmap, dim3(nblk(A.nzc, 256)), dim3(256), 0, m.s, A.nzc, A.cp, A.jc, cmap.p, clen8.p);
+  }
+}
+
+// c_dbg, once per device (it exists once per device; a pageable copy holds the host ~20 us)
+static void upload_dbg_mask(hipStream_t s) {
+  static const int dbg = dbg_mask();
+  static std::atomic<unsigned long long> dbg_set{0};
+  if (!dbg) return;
+  int dev = 0;
+  CBG_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(dbg_set.fetch_or(bit) & bit))
+    CBG_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_dbg), &dbg, sizeof(int), 0, hipMemcpyHostToDevice, s));
+}
+
+// The lower cut (LOW_CUT_FLOPS above), decided on the host's copy of the
+// symbolic histogram: where it applies, the multiply runs from here on as under
+// CBG_BIG_FLOPS=1024 -- the bins' columns move in the scatter (sp.remap), the
+// histogram moves with them here.  thr: the symbolic bins' thresholds.
+// Returns whether the cut was taken.
+static bool take_lower_cut(BinPending& sp, const int64_t* thr, int thin_R) {
+  static_assert(GROUP_PRODUCTS >= 4096, "one group class takes every column of the rerouted bins");
+  unsigned long long all_f = 0, big_f = 0;
+  int moved = 0;
+  for (int b = 0; b <= THIN_BIN; ++b) all_f += sp.hf[b];
+  for (int b = NSMALL; b <= THIN_BIN; ++b) big_f += sp.hf[b];
+  for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) moved += sp.h[b];
+  const unsigned long long thin_f = sp.hf[THIN_BIN] + sp.lo_stats[3];
+  const bool thin_fits =
+      !thin_R || !sp.lo_stats[2] || (double)thin_f * THIN_BYTES_PER_PRODUCT <= 0.25 * device_bytes_available();
+  if (!(moved > 0 && big_f * LOW_CUT_DEN >= all_f * LOW_CUT_NUM && thin_fits)) return false;
+  int to = NSMALL + NGCLS - 1;  // the first group class in use: thr >= GROUP_PRODUCTS >= their flops
+  for (int c = NGCLS - 2; c >= 0; --c)
+    if (thr[NSMALL + c] >= 0) to = NSMALL + c;
+  const int nthin = (int)sp.lo_stats[2];
+  unsigned long long moved_f = 0;
+  for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) {
+    moved_f += sp.hf[b];
+    sp.h[b] = 0;
+    sp.hf[b] = 0;
+  }
+  sp.h[to] += moved - nthin;
+  sp.hf[to] += moved_f - sp.lo_stats[3];
+  sp.h[THIN_BIN] += nthin;
+  sp.hf[THIN_BIN] += sp.lo_stats[3];
+  sp.big_entries[0] += sp.lo_stats[0];
+  sp.big_entries[1] += sp.lo_stats[1];
+  sp.remap.lo = LOW_CUT_BIN0;
+  sp.remap.hi = LOW_CUT_BIN1;
+  sp.remap.to = to;
+  sp.remap.thin_bin = THIN_BIN;
+  sp.remap.nthin = nthin;
+  return true;
+}
+
+// Stage 2: flops per B column and the symbolic's bins (host sync 1 of 4)
+static void plan_symbolic_bins(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  const hipStream_t s = m.s;
+  const int64_t nz = m.nz;
+  BigPlan& bp = m.bp;
+  m.flops.reset(nz + 1);
+  launch_flops(B, m.cmap().p, m.clen8().p, A.nnz == A.n && A.nzc == A.n, m.flops.p, s, m.df);
+  m.cnt.reset(nz + 1);
+  CBG_HIP(hipMemsetAsync(m.cnt.p, 0, sizeof(int32_t) * (nz + 1), s));
+  bool big_fixed = false;
+  m.big = big_flops(A.m, &big_fixed);
+  upload_dbg_mask(s);
+  bp.plog = pick_panel_log(A.m);
+  bp.R = (int)((A.m + (1LL << bp.plog) - 1) >> bp.plog);
+  static const char* eg = getenv("CBG_GROUPS");
+  const bool groups = !(eg && !strcmp(eg, "0"));
+  const int64_t gp = GROUP_PRODUCTS;
+  int64_t thr[NSMALL + NGCLS];
+  for (int i = 0; i < NSMALL; ++i) thr[i] = std::min(kSymThr[i], m.big);
+  thr[NSMALL + NGCLS - 1] = INT64_MAX;  // the single-panel big columns; bin NSMALL + NGCLS: thin ones
+  const int glmax = GROUP_LOG_MAX;
+  for (int c = 0; c + 1 < NGCLS; ++c) {
+    const int64_t g = 1LL << (GROUP_LOG_MAX - c);
+    thr[NSMALL + c] = (groups && g <= bp.R && g <= (1LL << glmax)) ? gp * bp.R / g : -1;
+  }
+  BinPending sp;
+  const bool thin_on = !(getenv("CBG_THIN") && !strcmp(getenv("CBG_THIN"), "0"));  // read per call (tests)
+  // thin when flops * THIN_RATIO < B entries * R (1 and 2 measured equal at scales 22/24)
+  const int ratio = (int)THIN_RATIO;
+  m.thin_R = (thin_on && bp.R >= 4) ? (int)(bp.R * THIN_RATIO / ratio) : 0;
+  // condition (a) of the lower cut; (b) needs the bins' flops
+  const int64_t low = (!big_fixed && m.big > LOW_CUT_FLOPS && A.m <= (1LL << GRANK_SPAN_LOG)) ? LOW_CUT_FLOPS : 0;
+  bin_classify(nz, m.flops.p, m.cnt.p, 0, thr, NSMALL + NGCLS, m.big, sp, s, 0, B.cp, NSMALL, m.thin_R, THIN_BIN, low);
+  CBG_HIP(hipStreamSynchronize(s));  // host sync 1 of 4: the symbolic bins' sizes
+  sp.read();
+  if (m.thin_R && (double)sp.hf[THIN_BIN] * THIN_BYTES_PER_PRODUCT > 0.25 * device_bytes_available()) {
+    // the sort's temporaries (64-bit counts, cbg_sort.hip) would take more than a
+    // quarter of the device memory left: classify again without thin columns
+    m.thin_R = 0;
+    bin_classify(nz, m.flops.p, m.cnt.p, 0, thr, NSMALL + NGCLS, m.big, sp, s, 0, B.cp, NSMALL, 0, THIN_BIN, low);
+    CBG_HIP(hipStreamSynchronize(s));
+    sp.read();
+  }
+  if (low > 0 && take_lower_cut(sp, thr, m.thin_R)) m.big = LOW_CUT_FLOPS;
+  m.work[CBG_WORK_BIG_CUT] = m.big;
+  bin_scatter(nz, sp, m.sb, s, m.df);
+  m.big_entries = (int64_t)sp.big_entries[0];
+  m.thin_entries = (int64_t)sp.big_entries[1];
+  bp.nbig = m.sb.offset[NSMALL + NGCLS] - m.sb.offset[NSMALL];
+  bp.perm_big = m.sb.perm.p + m.sb.offset[NSMALL];
+}
+
+// Stage 3: the small columns' symbolic -- the fused bins' expand-sort-compress
+// (with their numeric) and the block hash bins -- on the side stream, beside
+// the big columns on the main one
+static void sym_small_columns(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  const hipStream_t s = m.s;
+  const Binned& sb = m.sb;
+  // slot width of fused bin b: its flops bound (big >= 64 never clips bins 1..6,
+  // and a clipped bin 7 .. 9 holds columns of <= big flops)
+  auto fmax_of = [&](int b) { return (int)kSymThr[b]; };
+  m.fused_slot.reset(m.nz);
+  CBG_HIP(hipMemsetAsync(m.fused_slot.p, 0xff, sizeof(int64_t) * m.nz, s));  // -1: not fused (before the fork)
+  // inline records of A's columns for the small-column and thin passes when A's
+  // columns are short (<= 2 entries on average) and each entry is gathered many
+  // times (flops >= 4 nnz(A)): GalerkinNew's S*(AT), S = T^T
+  unsigned long long fsmall = 0;
+  for (int b = 1; b < NSMALL; ++b) fsmall += sb.flops[b];
+  fsmall += m.thin_R ? sb.flops[THIN_BIN] : 0;
+  if (A.nnz <= 2 * A.nzc && (double)fsmall >= 4.0 * (double)A.nnz) {
+    m.ainl.reset(2 * (A.n + 1));
+    hipLaunchKernelGGL(k_inline_cols, dim3(nblk(A.n + 1, 256)), dim3(256), 0, s, A.n + 1, m.cmap().p, A.ir, A.val,
+                       m.ainl.p);
+  }
+  m.ts.fork(s);
+  // streams of the small symbolic bins (balance_bins; the fused bins also do
+  // their numeric work: cost 2 per flop)
+  hipStream_t symst[NSMALL];
+  double main_w = 0.0;
+  for (int b = NSMALL; b < NSMALL + NGCLS; ++b) main_w += (double)sb.flops[b];
+  double cost[NSMALL];
+  for (int b = 0; b < NSMALL; ++b) cost[b] = (b >= 1 && b <= SYM_FUSED_LAST) ? 2.0 : 1.0;
+  // The small symbolic bins join the main stream, ahead of
+  // the (column, panel) units, when those carry most of the flops over >= 8
+  // row panels -- on the side stream they co-ran with k_sym_panel for its
+  // whole length and slowed it (scale 22: 436.3 vs 443.1 ms, scale 24:
+  // 3948 vs 3965 ms); small products (scale 18: R = 1) and small-column
+  // products (GalerkinNew) keep the concurrency (side: 6.67 vs 6.79 ms and
+  // 6.37 vs 6.85 ms)
+  if (m.bp.R >= 8) {
+    double small_w = 0.0;
+    for (int b = 1; b < NSMALL; ++b) small_w += (double)sb.flops[b];
+    m.big_dominant = main_w >= small_w;
+  }
+  const hipStream_t sy = m.big_dominant ? s : m.ts.side;
+  symst[0] = sy;
+  balance_bins(sb.flops, 1, NSMALL - 1, main_w, 0.0, cost, s, sy, symst, !m.big_dominant);
+  const int32_t* P = sb.perm.p;
+  auto at = [&](int b) { return P + sb.offset[b]; };
+  // bins 1..SYM_FUSED_LAST (flops <= 512): symbolic and numeric in one pass into fused_ir/val
+  for (int b = 1; b <= SYM_FUSED_LAST; ++b)
+    m.fused_off[b + 1] = m.fused_off[b] + (size_t)sb.count[b] * (size_t)fmax_of(b);
+  // the thin columns' unique entries follow the fused bins' slots
+  const size_t ftot = m.fused_off[SYM_FUSED_LAST + 1] + (m.thin_R ? (size_t)sb.flops[THIN_BIN] : 0);
+  m.fused_ir.reset(ftot + 1);
+  m.fused_val.reset(ftot + 1);
+  with_semiring(m.semiring, [&](auto sr) {
+    for (int b = 1; b <= SYM_FUSED_LAST; ++b)
+      launch_esc<decltype(sr)::value>(at(b), sb.count[b], fmax_of(b), B, m.cmap().p, m.ainl.p, A, m.cnt.p,
+                                      m.fused_ir.p, m.fused_val.p, (int64_t)m.fused_off[b], m.fused_slot.p, symst[b]);
+  });
+  launch_sym_block<11, 256>(at(10), sb.count[10], B, m.cmap().p, m.ainl.p, A, m.cnt.p, symst[10]);
+  launch_sym_block<12, 256>(at(11), sb.count[11], B, m.cmap().p, m.ainl.p, A, m.cnt.p, symst[11]);
+  launch_sym_block<13, 512>(at(12), sb.count[12], B, m.cmap().p, m.ainl.p, A, m.cnt.p, symst[12]);
+}
+
+// Stage 4: A's values as f32 for the slab kernels, and whether A and B are
+// integral (IACC): checked once per A, the verdicts are read back with host sync 2
+static void check_values(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  const hipStream_t s = m.s;
+  const int nbig = m.bp.nbig;
+  m.af = m.ap.active ? m.ap.af : -1;
+  m.ai = m.ap.active ? m.ap.ai : -1;
+  m.amax = m.ap.active ? m.ap.amax : 0;
+  m.afh = reinterpret_cast<int*>(host_stage(STAGE_AF));
+  if (nbig > 0 && m.af < 0 && !m.sym_only) {
+    m.valf().reset(A.nnz);
+    m.valp().reset(A.nnz);
+    m.af_flag.reset(4);  // ([3]: k_int_bound's unused column-sum slot)
+    CBG_HIP(hipMemsetAsync(m.af_flag.p, 0, 4 * sizeof(int), s));
+    const int64_t nb = std::min<int64_t>(nblk(A.nnz, 256), (int64_t)device_cus() * 16);
+    hipLaunchKernelGGL(k_vals_f32, dim3((unsigned)nb), dim3(256), 0, s, A.nnz, A.val, m.valf().p, m.af_flag.p, A.ir,
+                       m.valp().p);
+    hipLaunchKernelGGL(k_int_bound, dim3((unsigned)nb), dim3(256), 0, s, A.nnz, A.val, m.af_flag.p + 1, m.af_flag.p);
+    CBG_HIP(hipMemcpyAsync(m.afh, m.af_flag.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  m.afh[4] = 1;  // (no check: not integral)
+  if (nbig > 0 && !m.sym_only && m.af != 0 && m.ai != 0) {
+    m.bint.reset(3);
+    CBG_HIP(hipMemsetAsync(m.bint.p, 0, 3 * sizeof(int), s));
+    hipLaunchKernelGGL(k_col_int_bound,
+                       dim3((unsigned)std::min<int64_t>(nblk(B.nzc * WAVE, 256), (int64_t)device_cus() * 8)), dim3(256),
+                       0, s, B.nzc, B.cp, B.val, m.bint.p, m.af_flag.p);
+    CBG_HIP(hipMemcpyAsync(m.afh + 4, m.bint.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+}
+
+// panel column maps of A (reused across phases like cmap)
+static void prep_panel_maps(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  const hipStream_t s = m.s;
+  APrep& ap = m.ap;
+  BigPlan& bp = m.bp;
+  constexpr int pm_entries = 64;  // map only the referenced A columns when big-column entries * 64 < A's columns
+  bp.n1 = A.n + 1;
+  // column-major panel maps for the symbolic's XCD column order: a column's R
+  // entries in one or two lines (scale 22: 399.6 -> 395.5 ms alone, with the
+  // order 384 ms; the numeric slabs, panel-major, read them at the same speed)
+  bp.kmajor = bp.R > 1;
+  if (ap.active && ap.cmapP.p && ap.plog == bp.plog && ap.kmajor == bp.kmajor) {
+    bp.cmapP = ap.cmapP.p;
+  } else if (bp.R > 1 && pm_entries > 0 && m.big_entries * pm_entries < A.nzc) {
+    // few big-column entries (GalerkinNew's A*T: ~10^3 of A's 4 M columns;
+    // not the phase plan's sample of scale 22, 1/10 of them, whose hub
+    // references would each search their long A column again):
+    // map only the A columns they reference, without the memset of the
+    // R x n map; this B's own map, never cached for other pieces / phases
+    bp.cmapP_own.reset((size_t)bp.R * (A.n + 1));
+    hipLaunchKernelGGL(k_colmap_panels_entries, dim3(nblk((int64_t)bp.nbig * WAVE, 256)), dim3(256), 0, s,
+                       bp.perm_big, bp.nbig, B.cp, B.ir, m.cmap().p, A.ir, bp.plog, bp.R, bp.pm().sr, bp.pm().sk,
+                       bp.cmapP_own.p);
+    bp.cmapP = bp.cmapP_own.p;
+  } else {
+    DBuf<int2>& cp = ap.active ? ap.cmapP : bp.cmapP_own;
+    cp.reset((size_t)bp.R * (A.n + 1));
+    if (bp.R == 1) {
+      hipLaunchKernelGGL(k_colmap_panel1, dim3(nblk(A.n + 1, 256)), dim3(256), 0, s, A.n + 1, m.cmap().p, cp.p);
+    } else {
+      CBG_HIP(hipMemsetAsync(cp.p, 0, sizeof(int2) * bp.R * (A.n + 1), s));
+      hipLaunchKernelGGL(k_colmap_panels_col, dim3(nblk(A.nzc, 256)), dim3(256), 0, s, A.nzc, A.cp, A.jc, A.ir,
+                         bp.plog, bp.R, bp.pm().sr, bp.pm().sk, cp.p);
+    }
+    if (ap.active) {
+      ap.plog = bp.plog;
+      ap.kmajor = bp.kmajor;
+    }
+    bp.cmapP = cp.p;
+  }
+}
+
+// Stage 5: the big columns' symbolic on the main stream: A's panel maps, the
+// kept-bitmap and cut budgets, one k_sym_panel launch per group class, the
+// deferred group units
+static void sym_big_columns(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  const hipStream_t s = m.s;
+  const Binned& sb = m.sb;
+  BigPlan& bp = m.bp;
+  DeferredFree& df = m.df;
+  const int nbig = bp.nbig;
+  if (nbig <= 0) return;
+  const int64_t nbr = (int64_t)nbig * bp.R;
+  prep_panel_maps(m);
+  bp.desc.reset((size_t)nbr * NFINE_MAX);
+  bp.nslab.reset(nbr);
+  bp.cnt_br.reset(nbr);
+  // keep the symbolic bitmaps for the numeric phase when they fit a budget
+  // (saves the numeric marking pass); otherwise numeric rebuilds them
+  // slots are handed out in launch order by the bitmap-mode pairs
+  const int64_t slot_bytes = (int64_t)4 << (bp.plog - 5);
+  const int64_t nslots = m.sym_only ? 0 : std::min<int64_t>(nbr, (int64_t)(bitmap_budget_bytes() / slot_bytes));
+  DBuf<int> gbm_next;
+  if (nslots > 0) {
+    bp.gbm.reset((size_t)nslots << (bp.plog - 5));
+    bp.gbm_slot.reset(nbr);
+    gbm_next.reset(1);
+    CBG_HIP(hipMemsetAsync(gbm_next.p, 0, sizeof(int), s));
+  }
+  if (nbr >= (int64_t)INT32_MAX) throw HipError("too many (column, panel) pairs", CBG_ERR_NOTSUPPORTED);
+  // the multi-slab pairs' cut positions, handed out by an atomic counter up to
+  // a budget (pairs past it leave their cuts to the numeric's searches)
+  DBuf<unsigned long long> cuts_next;
+  long long cuts_cap = 0;
+  if (!m.sym_only) {
+    // at most min(1.5 GB, 2 % of the free HBM), and never more than the cuts of
+    // every pair cut into NFINE_MAX slabs (GalerkinNew's few big columns need
+    // little); CBG_CUTS_CAP (entries, read per call) is a test hook that leaves
+    // pairs past it to the numeric's searches
+    cuts_cap = std::min<long long>(INT32_MAX, (long long)(std::min(1.5e9, 0.02 * device_bytes_available()) / 4));
+    cuts_cap = std::min<long long>(cuts_cap, (long long)m.big_entries * bp.R * (NFINE_MAX - 1));
+    if (const char* e = getenv("CBG_CUTS_CAP")) cuts_cap = std::min<long long>(cuts_cap, atoll(e));
+    bp.cuts.reset(std::max<long long>(cuts_cap, 1));
+    bp.pcoff.reset(nbr);
+    cuts_next.reset(1);
+    CBG_HIP(hipMemsetAsync(bp.pcoff.p, 0xff, sizeof(int) * nbr, s));
+    CBG_HIP(hipMemsetAsync(cuts_next.p, 0, sizeof(unsigned long long), s));
+  }
+  const int pwords = 1 << (bp.plog - 5);
+  auto lds_of = [&](int hw) {
+    return (size_t)hw * 4 + NFINE_MAX * 4 + (BIG_BS + 4) * 4 + BIG_BS * 4 + (BIG_BS / WAVE + 4) * 4 +
+           (size_t)SYM_OVF_CAP * 4;
+  };
+  set_lds(k_sym_panel<true>, lds_of(std::max(pwords, GROUP_T)));
+  set_lds(k_sym_panel<false>, lds_of(std::max(pwords, GROUP_T)));
+  SymPanelArgs sa{bp.perm_big, bp.R, bp.plog, 0, 0, pwords, 0, B.cp, B.ir, bp.pm(), A.ir, A.m,
+                  m.cnt.p, bp.cnt_br.p, bp.desc.p, bp.nslab.p, bp.gbm.p, (int)nslots, gbm_next.p,
+                  bp.gbm_slot.p,
+                  bp.cuts.p, cuts_next.p, cuts_cap,
+                  bp.pcoff.p, nullptr, nullptr};
+  // group units that overflow one hash slab, collected for k_sym_deferred
+  int64_t group_units = 0;
+  for (int c = 0; c < NGCLS; ++c)
+    if (GROUP_LOG_MAX - c > 0)
+      group_units += (int64_t)sb.count[NSMALL + c] * ((bp.R + (1 << (GROUP_LOG_MAX - c)) - 1) >> (GROUP_LOG_MAX - c));
+  DBuf<int4> defer;
+  DBuf<int> defer_n;
+  if (group_units > 0) {
+    defer.reset(group_units);
+    defer_n.reset(1);
+    CBG_HIP(hipMemsetAsync(defer_n.p, 0, sizeof(int), s));
+    sa.defer = defer.p;
+    sa.defer_n = defer_n.p;
+  }
+  // one launch per group class (largest groups first)
+  for (int c = 0; c < NGCLS; ++c) {
+    const int nc = sb.count[NSMALL + c];
+    if (nc == 0) continue;
+    sa.glog = GROUP_LOG_MAX - c;
+    sa.boff = sb.offset[NSMALL + c] - sb.offset[NSMALL];
+    sa.hwords = sa.glog > 0 ? std::max(pwords, GROUP_T) : pwords;
+    const int64_t RG = (bp.R + (1 << sa.glog) - 1) >> sa.glog;
+    sa.ncls = nc;
+    m.work[sa.glog > 0 ? CBG_WORK_SYM_GROUP_UNITS : CBG_WORK_SYM_PANEL_UNITS] += RG * nc;
+    // resident blocks per CU at this launch's LDS size
+    const int per_cu = sa.glog > 0 ? blocks_per_cu(k_sym_panel<true>, BIG_BS, lds_of(sa.hwords))
+                                   : blocks_per_cu(k_sym_panel<false>, BIG_BS, lds_of(sa.hwords));
+    // (a multiple of 8: the XCD column order; 8 x ceil(nc / 8) x RG units)
+    const int64_t grid = std::min<int64_t>(RG * ((nc + 7) / 8) * 8,
+                                           ((int64_t)per_cu * device_cus() * CBG_SYM_WAVES_OF_UNITS) & ~7LL);
+    if (sa.glog > 0)
+      hipLaunchKernelGGL(k_sym_panel<true>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    else
+      hipLaunchKernelGGL(k_sym_panel<false>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+  }
+  if (group_units > 0) {
+    sa.hwords = std::max(pwords, GROUP_T);
+    set_lds(k_sym_deferred, lds_of(sa.hwords));
+    hipLaunchKernelGGL(k_sym_deferred, dim3((unsigned)std::min<int64_t>(group_units, device_cus() * 4)),
+                       dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    CBG_HIP(hipMemcpyAsync(reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS)) + 5, defer_n.p, sizeof(int),
+                           hipMemcpyDeviceToHost, s));
+    df.take(defer);
+    df.take(defer_n);
+  }
+  // the symbolic kernels may still run: the counters stay allocated until the
+  // multiply's last synchronization
+  bp.gbm_next = gbm_next.p;
+  bp.gbm_slots = nslots;
+  df.take(gbm_next);
+  df.take(cuts_next);
+}
+
+// CBG_DBG bit 16: the symbolic bins' sizes
+static void dbg_report_bins(const LocalMul& m) {
+  const Binned& sb = m.sb;
+  unsigned long long fs = 0, fh = 0, fb = 0;
+  for (int b = 1; b <= SYM_FUSED_LAST; ++b) fs += sb.flops[b];
+  for (int b = SYM_FUSED_LAST + 1; b < NSMALL; ++b) fh += sb.flops[b];
+  for (int b = NSMALL; b < NSMALL + NGCLS; ++b) fb += sb.flops[b];
+  std::fprintf(stderr,
+               "[cbg bins] fused cols %d flops %llu | hash cols %d flops %llu | big cols %d flops %llu | "
+               "thin cols %d entries %lld flops %llu | inline A %d\n",
+               sb.offset[SYM_FUSED_LAST + 1] - sb.offset[1], fs, sb.offset[NSMALL] - sb.offset[SYM_FUSED_LAST + 1],
+               fh, m.bp.nbig, fb, m.thin_R ? sb.count[THIN_BIN] : 0, (long long)m.thin_entries,
+               m.thin_R ? (unsigned long long)sb.flops[THIN_BIN] : 0ull, m.ainl.p != nullptr);
+}
+
+// Stage 6: the thin columns' sort after the big columns' launches (its host
+// synchronizations would otherwise hold them back); the symbolic's streams join
+static void sym_thin_columns(LocalMul& m) {
+  const Binned& sb = m.sb;
+  if (m.thin_R && sb.count[THIN_BIN] > 0) {
+    // on the copy stream (idle until the numeric), from the fork point, so the
+    // sort runs beside the small-column bins of both streams instead of behind
+    // the main stream's (its readback then waits for the sort alone)
+    CBG_HIP(hipStreamWaitEvent(m.ts.scopy, m.ts.ev_fork, 0));
+    thin_columns(sb.perm.p + sb.offset[THIN_BIN], sb.count[THIN_BIN], m.thin_entries, (int64_t)sb.flops[THIN_BIN], m.A,
+                 m.B, m.cmap().p, m.ainl.p, m.semiring, m.cnt.p, m.fused_slot.p, m.fused_ir.p, m.fused_val.p,
+                 (int64_t)m.fused_off[SYM_FUSED_LAST + 1], m.ts.scopy, m.df);
+    m.ts.join_copy(m.s);
+  }
+  m.ts.join(m.s);
+}
+
+// Stage 7: everything that depends only on the per-column counts is launched
+// now and read back in ONE synchronization (host sync 2 of 4): nnz(C) (column
+// pointers), the number of slabs, the numeric bins' histogram and the number
+// of nonempty C columns.
+static void scan_counts(LocalMul& m) {
+  const cbg_tile& B = m.B;
+  const hipStream_t s = m.s;
+  const int64_t nz = m.nz;
+  BigPlan& bp = m.bp;
+  DeferredFree& df = m.df;
+  const int64_t nbr = (int64_t)bp.nbig * bp.R;
+  m.colptr.reset(nz + 1);
+  exclusive_scan_i32_to_i64(m.cnt.p, m.colptr.p, nz, s, &df);
+  // nnz(C), slabs, nonempty C columns, flops: one pinned slot, read after sync 2
+  int64_t* scal = reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS));
+  scal[1] = 0;
+  CBG_HIP(hipMemcpyAsync(&scal[0], m.colptr.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  // slab lists of big columns
+  if (bp.nbig > 0) {
+    m.sbase.reset(nbr + 1);
+    exclusive_scan_i32_to_i64(bp.nslab.p, m.sbase.p, nbr, s, &df);
+    CBG_HIP(hipMemcpyAsync(&scal[1], m.sbase.p + nbr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  }
+  bin_classify(nz, m.flops.p, m.cnt.p, 1, kNumThr, 9, m.big, m.npend, s, kSymThr[SYM_FUSED_LAST], B.cp, MAXBINS,
+               m.thin_R, 0);
+  // compaction of C's columns (SpDCCols(SpTuples): nonempty columns only)
+  m.flag.reset(nz + 1);
+  m.pos.reset(nz + 1);
+  hipLaunchKernelGGL(k_col_flags, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, m.cnt.p, m.flag.p);
+  exclusive_scan_i64(m.flag.p, m.pos.p, nz, s, &df);
+  CBG_HIP(hipMemcpyAsync(&scal[2], m.pos.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  CBG_HIP(hipMemcpyAsync(&scal[3], m.flops.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  // single-entry big columns: their sizes' scan (the chunked copy), total read back with sync 2
+  scal[4] = 0;
+  if (!m.sym_only) {
+    m.sb_sz.reset(nz);
+    m.sb_off.reset(nz + 1);
+    hipLaunchKernelGGL(k_single_big_sizes, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, B.cp, m.flops.p, m.big,
+                       m.sb_sz.p);
+    exclusive_scan_i64(m.sb_sz.p, m.sb_off.p, nz, s, &df);
+    CBG_HIP(hipMemcpyAsync(&scal[4], m.sb_off.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  }
+  CBG_HIP(hipEventRecord(m.ts.ev1, s));
+  CBG_HIP(hipStreamSynchronize(s));  // host sync 2 of 4
+  m.nnzc = scal[0];
+  m.nslabs = scal[1];
+  m.nzcC = scal[2];
+  m.flops_total = scal[3];
+  m.single_big_entries = scal[4];
+  m.work[CBG_WORK_SYM_DEFERRED_UNITS] = scal[5];
+  for (int b = 1; b <= SYM_FUSED_LAST; ++b) m.work[CBG_WORK_ESC_COLUMNS] += m.sb.count[b];
+  m.work[CBG_WORK_THIN_COLUMNS] = m.thin_R ? m.sb.count[THIN_BIN] : 0;
+  m.work[CBG_WORK_SINGLE_BIG_ENTRIES] = m.single_big_entries;
+}
+
+// the value format of A the slab kernels read, from the verdicts of check_values
+static void pick_value_format(LocalMul& m) {
+  const cbg_tile& A = m.A;
+  APrep& ap = m.ap;
+  BigPlan& bp = m.bp;
+  if (m.af_flag.p) {
+    const int af_inexact = m.afh[0];
+    m.af = af_inexact ? 0 : 1;
+    m.ai = m.afh[1] ? 0 : 1;
+    m.amax = m.afh[2];
+    if (ap.active) {
+      ap.af = m.af;
+      ap.ai = m.ai;
+      ap.amax = m.amax;
+    }
+    if (!m.af) {
+      m.valf().release();
+      m.valp().release();
+    }
+  }
+  if (m.af == 1) bp.valAf = m.valf().p;
+  if (m.af == 1 && m.valp().p) bp.valAp = m.valp().p;
+  uint64_t big_fl = 0;
+  for (int b = NSMALL; b < NSMALL + NGCLS; ++b) big_fl += m.sb.flops[b];
+  DBuf<PackedRVD>& vd = m.valpd();
+  if (m.af == 0 && bp.nbig > 0 && (vd.p || big_fl >= 4 * (uint64_t)A.nnz)) {
+    // the f64-valued slab path reads A as (row, f64) records (built once per A,
+    // when the big columns' products are enough to pay for its 24 B per entry:
+    // GalerkinNew scale 22 packed 68 M entries, 0.34 ms, for 3.7 M products)
+    if (!vd.p) {
+      vd.reset(A.nnz);
+      hipLaunchKernelGGL(k_pack_rvd, dim3((unsigned)std::min<int64_t>(nblk(A.nnz, 256), (int64_t)device_cus() * 16)),
+                         dim3(256), 0, m.s, A.nnz, A.ir, A.val, vd.p);
+    }
+    bp.valAd = vd.p;
+  }
+  bp.iacc = bp.valAp && m.ai == 1 && !m.afh[4] && iacc_bound_ok(m.semiring, m.amax, m.afh[5], m.afh[6]);
+  m.work[CBG_WORK_IACC] = bp.iacc ? 1 : 0;
+}
+
+// the big columns' slabs sorted by class into slist (host sync 3 of 4: the classes' sizes)
+static void plan_slabs(LocalMul& m) {
+  const hipStream_t s = m.s;
+  BigPlan& bp = m.bp;
+  const int nbig = bp.nbig;
+  m.slist.reset(m.nslabs);
+  const int NK = SLAB_NCLS * slab_kr(bp.R);
+  DBuf<int> counters(2 * NK + SLAB_NCLS);  // counts[NK] | cursor[NK] | class totals
+  CBG_HIP(hipMemsetAsync(counters.p, 0, (2 * NK + SLAB_NCLS) * sizeof(int), s));
+  const int rank_span = 1 << bp.plog, rank_min = RANK_SLABS_MIN;
+  // (CBG_GRANK_MIN, read per call: group slabs of more nonzeros than this run
+  // as group rank slabs; -1 none)
+  const char* egm = getenv("CBG_GRANK_MIN");
+  const int grank_min = egm ? (atoi(egm) < 0 ? INT32_MAX : atoi(egm)) : GRANK_SLABS_MIN;
+  hipLaunchKernelGGL(k_slab_count, dim3(nblk(nbig, 256)), dim3(256), NK * sizeof(int), s, nbig, bp.R, bp.nslab.p,
+                     bp.cnt_br.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p);
+  hipLaunchKernelGGL(k_slab_bases, dim3(1), dim3(64), 0, s, bp.R, counters.p, counters.p + NK, counters.p + 2 * NK);
+  hipLaunchKernelGGL(k_slab_fill, dim3(nblk(nbig, 256)), dim3(256), 2 * NK * sizeof(int), s, nbig, bp.R,
+                     bp.nslab.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p + NK, m.slist.p,
+                     bp.perm_big, m.B.cp, m.colptr.p,
+                     bp.gbm_slot.p, bp.plog, m.A.m, bp.pcoff.p);
+  int* ncls_h = reinterpret_cast<int*>(host_stage(STAGE_SLABS));
+  CBG_HIP(hipMemcpyAsync(ncls_h, counters.p + 2 * NK, SLAB_NCLS * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (bp.gbm_next) CBG_HIP(hipMemcpyAsync(ncls_h + SLAB_NCLS, bp.gbm_next, sizeof(int), hipMemcpyDeviceToHost, s));
+  CBG_HIP(hipStreamSynchronize(s));  // host sync 3 of 4: the slab classes' sizes
+  const int* ncls = m.ncls;
+  std::memcpy(m.ncls, ncls_h, sizeof(int) * SLAB_NCLS);
+  // (CBG_DBG bit 128 hands out slots without storing the bitmaps: the
+  // marking pass must run)
+  bp.all_kept = bp.gbm_next && (int64_t)ncls_h[SLAB_NCLS] <= bp.gbm_slots && !(dbg_mask() & 128);
+  m.df.take(counters);
+  m.work[bp.all_kept ? CBG_WORK_BITMAP_SMALL_KEPT : CBG_WORK_BITMAP_SMALL_MARK] = ncls[0];
+  m.work[bp.all_kept ? CBG_WORK_BITMAP_LARGE_KEPT : CBG_WORK_BITMAP_LARGE_MARK] = ncls[1];
+  for (int k = 0; k < SLAB_HASH_NCLS; ++k) m.work[CBG_WORK_HASH0 + k] = ncls[2 + k];
+  for (int k = 0; k < SLAB_RANK_NCLS; ++k) m.work[CBG_WORK_RANK0 + k] = ncls[SLAB_RANK0 + k];
+  for (int k = 0; k < SLAB_GRANK_NCLS; ++k) m.work[CBG_WORK_GRANK0 + k] = ncls[SLAB_GRANK0 + k];
+  if (dbg_mask() & 16) {
+    static const int ht[SLAB_HASH_NCLS] = {CBG_HASH_TABLES};
+    std::fprintf(stderr, "[cbg slabs] bitmap small %d large %d | hash", ncls[0], ncls[1]);
+    for (int k = 0; k < SLAB_HASH_NCLS; ++k) std::fprintf(stderr, " T%d %d", ht[k], ncls[2 + k]);
+    std::fprintf(stderr, " | rank N1024 %d N2048 %d N4096 %d | group rank N2048 %d N4096 %d", ncls[SLAB_RANK0],
+                 ncls[SLAB_RANK0 + 1], ncls[SLAB_RANK0 + 2], ncls[SLAB_GRANK0], ncls[SLAB_GRANK0 + 1]);
+    std::fprintf(stderr, "\n");
+  }
+}
+
+// Stage 8: C's arrays, its column headers and the slab plan
+static void alloc_c_and_plan_slabs(LocalMul& m) {
+  cbg_tile& C = m.C;
+  // test hook (CBG_FAULT_C_BYTES, read per call): C larger than this fails as
+  // an out-of-memory would, after the symbolic pass -- the phase splitting of
+  // MemEfficientSpGEMM (cbg_summa.cpp multiply_to_fn) is tested with it
+  const char* e = getenv("CBG_FAULT_C_BYTES");
+  if (e && 12.0 * (double)m.nnzc > atof(e)) {
+    m.df.synced = true;
+    throw HipError("C of " + std::to_string(m.nnzc) + " entries exceeds CBG_FAULT_C_BYTES", CBG_ERR_OOM);
+  }
+  C.nzc = m.nzcC;
+  C.cp = static_cast<int64_t*>(pool().alloc(sizeof(int64_t) * (m.nzcC + 1)));
+  C.jc = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(m.nzcC, 1)));
+  m.Cg.t = C;
+  hipLaunchKernelGGL(k_col_scatter, dim3(nblk(m.nz + 1, 256)), dim3(256), 0, m.s, m.nz, m.cnt.p, m.pos.p, m.B.jc,
+                     m.colptr.p, C.jc, C.cp);
+  if (m.bp.nbig > 0 && m.nslabs > 0) plan_slabs(m);
+  // output arrays
+  C.nnz = m.nnzc;
+  if (m.sink) {
+    m.sink->place(m.nnzc, &C.ir, &C.val);
+    C.reserved |= TILE_BORROWED_ENTRIES;
+  } else {
+    C.ir = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(m.nnzc, 1)));
+    C.val = static_cast<double*>(pool().alloc(sizeof(double) * std::max<int64_t>(m.nnzc, 1)));
+  }
+  m.Cg.t = C;
+}
+
+// Stage 9: the numeric launches (host sync 4 of 4: C complete)
+static void numeric(LocalMul& m) {
+  const cbg_tile &A = m.A, &B = m.B;
+  cbg_tile& C = m.C;
+  const hipStream_t s = m.s, side = m.ts.side, scopy = m.ts.scopy;
+  const int64_t nz = m.nz;
+  const Binned& sb = m.sb;
+  BigPlan& bp = m.bp;
+  DeferredFree& df = m.df;
+  Binned& nbn = m.nbn;
+  bin_scatter(nz, m.npend, nbn, s, df);
+  for (int b = 1; b <= 4; ++b) m.work[CBG_WORK_WAVE_BIN_COLUMNS] += nbn.count[b];
+  for (int b = 5; b <= 8; ++b) m.work[CBG_WORK_HASH_BIN_COLUMNS] += nbn.count[b];
+  // small-column bins on the side stream, big-column slabs on the main one,
+  // the copies (fused bins, single-entry columns) on the copy stream: they only
+  // need colptr and stream at HBM rate beside the latency-bound kernels
+  // (GalerkinNew at 22: 5.92 / 5.98 vs 6.45 / 6.38 ms); not where the big
+  // columns' slabs dominate, which they slow (scale 22: 418.4 vs 413.0 ms)
+  const bool copy_stream = !m.big_dominant;
+  m.ts.fork(s);
+  const hipStream_t sc = copy_stream ? scopy : side;
+  if (copy_stream) CBG_HIP(hipStreamWaitEvent(scopy, m.ts.ev_fork, 0));
+  hipStream_t numst[10];
+  // the slabs of the big columns on the main stream; the fused bins' copies on
+  // the side one (about a quarter of a product's cost per entry)
+  double fused_w = 0.0;
+  if (!copy_stream)
+    for (int b = 1; b <= SYM_FUSED_LAST; ++b) fused_w += 0.25 * (double)sb.flops[b];
+  numst[0] = numst[9] = side;
+  // balanced when the copies have their own stream (GalerkinNew 6.01 vs 6.07 ms,
+  // 3 rounds; round 3, before the copy stream: 9.9-10.2 vs 10.0 ms, off)
+  balance_bins(nbn.flops, 1, 8, (double)nbn.flops[9], fused_w, nullptr, s, side, numst, copy_stream);
+  // (the whole-column bins on the side stream overlap the slabs: serialized after
+  // them on the main stream they take ~13 ms per scale-22 step and the step is
+  // 1 ms longer, before them 0.6 ms longer -- profiles/r06_ab_numbins.json)
+  with_semiring(m.semiring, [&](auto sr) {
+    constexpr int SR = decltype(sr)::value;
+    const int2* cmap = m.cmap().p;
+    numeric_dispatch<SR>(nbn, A, bp.valAf, B, cmap, m.ainl.p, m.colptr.p, C, numst, df);
+    if (m.fused_off[SYM_FUSED_LAST + 1] > 0 || (m.thin_R && sb.count[THIN_BIN] > 0)) {
+      hipLaunchKernelGGL(k_copy_fused, dim3(nblk(nz, 256)), dim3(256), 0, sc, nz, m.fused_slot.p, m.cnt.p, m.colptr.p,
+                         m.fused_ir.p, m.fused_val.p, C.ir, C.val, (int64_t)m.fused_off[SYM_FUSED_LAST + 1]);
+      if (m.thin_R)
+        thin_copy(sb.perm.p + sb.offset[THIN_BIN], sb.count[THIN_BIN], m.fused_slot.p, m.cnt.p, m.colptr.p,
+                  m.fused_ir.p, m.fused_val.p, C.ir, C.val, s);
+    }
+    // single-entry columns as scaled copies of A's columns (k_classify)
+    hipLaunchKernelGGL(k_copy_single<SR>, dim3(nblk(nz, 256)), dim3(256), 0, sc, nz, B.cp, B.ir, B.val, cmap,
+                       m.flops.p, m.big, A.ir, A.val, m.colptr.p, C.ir, C.val);
+    if (m.single_big_entries > 0) {
+      const int ch = (int)std::min<int64_t>(SB_CHUNK, m.big + 1);
+      const unsigned g = (unsigned)((m.single_big_entries + ch - 1) / ch);
+      hipLaunchKernelGGL(k_copy_single_big<SR>, dim3(g), dim3(256), 0, sc, nz, m.sb_off.p, ch, B.cp, B.ir, B.val, cmap,
+                         A.ir, A.val, m.colptr.p, C.ir, C.val);
+    }
+    if (m.nslabs > 0) launch_slabs<SR>(m.slist.p, m.ncls, bp, A, B, C, s, df);
+  });
+  m.ts.join(s);
+  if (copy_stream) m.ts.join_copy(s);
+  CBG_HIP(hipEventRecord(m.ts.ev2, s));
+  CBG_HIP(hipStreamSynchronize(s));  // host sync 4 of 4: C complete
+  df.synced = true;
+  CBG_HIP(hipGetLastError());
+}
+
+// Stage 10 (CBG_DBG bit 16): the kernels' phase times and, with bit 32, their counters
+static void dbg_report_kernels() {
+  const int dbg = dbg_mask();
+  if (!(dbg & 16)) return;
+  if (dbg & 32) {
+    unsigned long long gs[16];
+    CBG_HIP(hipMemcpyFromSymbol(gs, HIP_SYMBOL(g_stat), sizeof(gs)));
+    std::fprintf(stderr, "[cbg k_num_slab] slabs %llu nonfull %llu nb %llu nb_nonfull %llu nout %llu multichunk %llu "
+                 "products %llu | hash products panel %llu column %llu nout %llu | rank products %llu nout %llu"
+                 " | symbolic groups %llu products %llu, by panels %llu products %llu\n",
+                 gs[0], gs[1], gs[2], gs[3], gs[5], gs[6], gs[4], gs[7], gs[8], gs[9], gs[10], gs[11], gs[12], gs[13],
+                 gs[14], gs[15]);
+    std::memset(gs, 0, sizeof(gs));
+    CBG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_stat), gs, sizeof(gs)));
+  }
+  unsigned long long ph[24];
+  CBG_HIP(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_phase), sizeof(ph)));
+  const char* names[7] = {"init", "staging", "-", "rankscan", "pass0", "pass1", "output"};
+  std::fprintf(stderr, "[cbg phases, block-us summed / 256 CUs]");
+  for (int k = 0; k < 7; ++k)
+    if (k != 2) std::fprintf(stderr, " %s=%.3fms", names[k], ph[k] / 100.0 / 256.0 / 1000.0);
+  const char* snames[5] = {"sym_staging", "sym_hash", "sym_bitmap_products", "sym_counts_store", "sym_plan"};
+  for (int k = 8; k < 13; ++k) std::fprintf(stderr, " %s=%.3fms", snames[k - 8], ph[k] / 100.0 / 256.0 / 1000.0);
+  const char* hnames[4] = {"hash_clear", "hash_staging", "hash_products", "hash_emit"};
+  const int hk[4] = {7, 13, 14, 15};
+  for (int k = 0; k < 4; ++k) std::fprintf(stderr, " %s=%.3fms", hnames[k], ph[hk[k]] / 100.0 / 256.0 / 1000.0);
+  const char* rnames[5] = {"rank_stage", "rank_products", "rank_scan", "rank_acc", "rank_emit"};
+  for (int k = 0; k < 5; ++k) std::fprintf(stderr, " %s=%.3fms", rnames[k], ph[16 + k] / 100.0 / 256.0 / 1000.0);
+  std::fprintf(stderr, "\n");
+  std::memset(ph, 0, sizeof(ph));
+  CBG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), ph, sizeof(ph)));
+}
+
+// The multiply: four host synchronizations, the stages above in order
 void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_tile& C, hipStream_t s, LocalStats* st,
                        OutSink* sink, bool sym_only) {
   C = cbg_tile{};
@@ -3989,753 +4627,42 @@ void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_t
     if (st) *st = LocalStats{};
     return;
   }
-  TileGuard Cg;  // C's arrays until the multiply has completed (exceptions included)
-  DeferredFree df;
-  // side stream for the small-column bins (independent of the big columns)
-  // (and a copy stream for the numeric's direct copies into C)
-  static thread_local hipStream_t side = nullptr, scopy = nullptr;
-  static thread_local hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cjoin = nullptr;
-  if (!side) {
-    CBG_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    CBG_HIP(hipStreamCreateWithFlags(&scopy, hipStreamNonBlocking));
-    CBG_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    CBG_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    CBG_HIP(hipEventCreateWithFlags(&ev_cjoin, hipEventDisableTiming));
-  }
-  // the small-column bins of the symbolic and the numeric run on the side stream
-  // (serialized on the main one: -0.5 % at scale 22, -5 % at 18), the symbolic's
-  // on the main one where the big columns dominate (below)
-  const hipStream_t ssym = side, snum = side;
-  auto fork = [&](hipStream_t main) {
-    CBG_HIP(hipEventRecord(ev_fork, main));
-    CBG_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-  };
-  auto join = [&](hipStream_t main) {
-    CBG_HIP(hipEventRecord(ev_join, side));
-    CBG_HIP(hipStreamWaitEvent(main, ev_join, 0));
-  };
-  // timing events, created once per thread and reused by every multiply
-  static thread_local hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  if (!ev0) {
-    CBG_HIP(hipEventCreate(&ev0));
-    CBG_HIP(hipEventCreate(&ev1));
-    CBG_HIP(hipEventCreate(&ev2));
-  }
-  CBG_HIP(hipEventRecord(ev0, s));
-  const int64_t nz = B.nzc;
-  int64_t work[CBG_WORK_N] = {};  // cbg_last_work_stats
+  LocalMul m(A, B, semiring, C, s, sink, sym_only);
+  CBG_HIP(hipEventRecord(m.ts.ev0, s));
   reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS))[5] = 0;  // deferred group units (sync 2)
-  // A column map (reused across the phases of one MemEfficientSpGEMM)
-  APrep& ap = aprep();
-  const uint64_t ser_ir = ap.active ? pool().serial_of(A.ir) : 0, ser_cp = ap.active ? pool().serial_of(A.cp) : 0;
-  const bool a_hit = ap.active && ap.ir == A.ir && ap.cp == A.cp && ap.ser_ir == ser_ir && ap.ser_cp == ser_cp &&
-                     ap.nnz == A.nnz && ap.nzc == A.nzc && ap.m == A.m && ap.n == A.n;
-  if (ap.active && !a_hit) {
-    ap.cmap.release();
-    ap.clen8.release();
-    ap.cmapP.release();
-    ap.valf.release();
-    ap.valp.release();
-    ap.valpd.release();
-    ap.af = -1;
-    ap.ai = -1;
-    ap.ir = A.ir;
-    ap.cp = A.cp;
-    ap.ser_ir = ser_ir;
-    ap.ser_cp = ser_cp;
-    ap.nnz = A.nnz;
-    ap.nzc = A.nzc;
-    ap.m = A.m;
-    ap.n = A.n;
-    ap.plog = -1;
-  }
-  DBuf<int2> cmap_own;
-  DBuf<unsigned char> clen8_own;
-  DBuf<int2>& cmap = ap.active ? ap.cmap : cmap_own;
-  DBuf<unsigned char>& clen8 = ap.active ? ap.clen8 : clen8_own;
-  if (!a_hit) {
-    cmap.reset(A.n + 1);
-    clen8.reset(A.n + 1);
-    CBG_HIP(hipMemsetAsync(cmap.p, 0, sizeof(int2) * (A.n + 1), s));
-    CBG_HIP(hipMemsetAsync(clen8.p, 0, A.n + 1, s));
-    hipLaunchKernelGGL(k_colmap, dim3(nblk(A.nzc, 256)), dim3(256), 0, s, A.nzc, A.cp, A.jc, cmap.p, clen8.p);
-  }
-
-  // flops per B column
-  DBuf<int64_t> flops(nz + 1);
-  launch_flops(B, cmap.p, clen8.p, A.nnz == A.n && A.nzc == A.n, flops.p, s, df);
-  DBuf<int32_t> cnt(nz + 1);
-  CBG_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (nz + 1), s));
-  // symbolic
-  Binned sb;
-  bool big_fixed = false;
-  int64_t big = big_flops(A.m, &big_fixed);  // (lowered below where the rule takes the lower cut)
-  {
-    // once per device (c_dbg exists once per device; a pageable copy holds the host ~20 us)
-    static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
-    static std::atomic<unsigned long long> dbg_set{0};
-    if (dbg) {
-      int dev = 0;
-      CBG_HIP(hipGetDevice(&dev));
-      const unsigned long long bit = 1ull << (dev & 63);
-      if (!(dbg_set.fetch_or(bit) & bit))
-        CBG_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_dbg), &dbg, sizeof(int), 0, hipMemcpyHostToDevice, s));
-    }
-  }
-  // symbolic bins: kSymThr (clipped at `big`), then the big columns by panel
-  // group size 2^GROUP_LOG_MAX .. 1 (columns with F * g / R <= GROUP_PRODUCTS
-  // expected products per group; CBG_GROUPS=0 keeps every pair on its own)
-  BigPlan bp;
-  int64_t big_entries = 0, thin_entries = 0;  // B entries of the big / thin columns (read back with sync 1)
-  // small columns' symbolic and numeric in one pass (bins 1..SYM_FUSED_LAST)
-  constexpr bool fused = true;
-  // single-entry columns as scaled copies of A's columns (CBG_COPY1=0: off)
-  // (default 2: also those of more than `big` flops -- R-MAT columns whose one
-  // entry hits a hub -- instead of (column, panel) pairs: s22 446.4 -> 440.9 ms;
-  // 1: only the small ones)
-  constexpr int copy1 = 2;
-  bp.plog = pick_panel_log(A.m);
-  bp.R = (int)((A.m + (1LL << bp.plog) - 1) >> bp.plog);
-  constexpr int NSMALL = 13, NGCLS = GROUP_LOG_MAX + 1, THIN_BIN = NSMALL + NGCLS;
-  static_assert(THIN_BIN < MAXBINS, "bins");
-  int thin_R = 0;
-  {
-    static const char* eg = getenv("CBG_GROUPS");
-    const bool groups = !(eg && !strcmp(eg, "0"));
-    const int64_t gp = GROUP_PRODUCTS;
-    int64_t thr[NSMALL + NGCLS];
-    for (int i = 0; i < NSMALL; ++i) thr[i] = std::min(kSymThr[i], big);
-    thr[NSMALL + NGCLS - 1] = INT64_MAX;  // the single-panel big columns; bin NSMALL + NGCLS: thin ones
-    const int glmax = GROUP_LOG_MAX;
-    for (int c = 0; c + 1 < NGCLS; ++c) {
-      const int64_t g = 1LL << (GROUP_LOG_MAX - c);
-      thr[NSMALL + c] = (groups && g <= bp.R && g <= (1LL << glmax)) ? gp * bp.R / g : -1;
-    }
-    BinPending sp;
-    const bool thin_on = !(getenv("CBG_THIN") && !strcmp(getenv("CBG_THIN"), "0"));  // read per call (tests)
-    // thin when flops * THIN_RATIO < B entries * R (1 and 2 measured equal at scales 22/24)
-    const int ratio = (int)THIN_RATIO;
-    thin_R = (fused && thin_on && bp.R >= 4) ? (int)(bp.R * THIN_RATIO / ratio) : 0;
-    // condition (a) of the lower cut; (b) needs the bins' flops
-    const int64_t low = (!big_fixed && big > LOW_CUT_FLOPS && A.m <= (1LL << GRANK_SPAN_LOG)) ? LOW_CUT_FLOPS : 0;
-    bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, thin_R, THIN_BIN, copy1,
-                 low);
-    CBG_HIP(hipStreamSynchronize(s));  // host sync 1 of 4: the symbolic bins' sizes
-    sp.read();
-    if (thin_R && (double)sp.hf[THIN_BIN] * THIN_BYTES_PER_PRODUCT > 0.25 * device_bytes_available()) {
-      // the sort's temporaries (64-bit counts, cbg_sort.hip) would take more than a
-      // quarter of the device memory left: classify again without thin columns
-      thin_R = 0;
-      bin_classify(nz, flops.p, cnt.p, 0, thr, NSMALL + NGCLS, big, sp, s, 0, B.cp, NSMALL, 0, THIN_BIN, copy1,
-                   low);
-      CBG_HIP(hipStreamSynchronize(s));
-      sp.read();
-    }
-    if (low > 0) {
-      // the lower cut (LOW_CUT_FLOPS above): from here on the multiply runs as under
-      // CBG_BIG_FLOPS=1024 -- the bins' columns move in the scatter (BinRemap), the
-      // host's copy of the histogram moves with them
-      static_assert(GROUP_PRODUCTS >= 4096, "one group class takes every column of the rerouted bins");
-      unsigned long long all_f = 0, big_f = 0;
-      int moved = 0;
-      for (int b = 0; b <= THIN_BIN; ++b) all_f += sp.hf[b];
-      for (int b = NSMALL; b <= THIN_BIN; ++b) big_f += sp.hf[b];
-      for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) moved += sp.h[b];
-      const unsigned long long thin_f = sp.hf[THIN_BIN] + sp.lo_stats[3];
-      const bool thin_fits =
-          !thin_R || !sp.lo_stats[2] || (double)thin_f * THIN_BYTES_PER_PRODUCT <= 0.25 * device_bytes_available();
-      if (moved > 0 && big_f * LOW_CUT_DEN >= all_f * LOW_CUT_NUM && thin_fits) {
-        int to = NSMALL + NGCLS - 1;  // the first group class in use: thr >= GROUP_PRODUCTS >= their flops
-        for (int c = NGCLS - 2; c >= 0; --c)
-          if (thr[NSMALL + c] >= 0) to = NSMALL + c;
-        const int nthin = (int)sp.lo_stats[2];
-        unsigned long long moved_f = 0;
-        for (int b = LOW_CUT_BIN0; b < LOW_CUT_BIN1; ++b) {
-          moved_f += sp.hf[b];
-          sp.h[b] = 0;
-          sp.hf[b] = 0;
-        }
-        sp.h[to] += moved - nthin;
-        sp.hf[to] += moved_f - sp.lo_stats[3];
-        sp.h[THIN_BIN] += nthin;
-        sp.hf[THIN_BIN] += sp.lo_stats[3];
-        sp.big_entries[0] += sp.lo_stats[0];
-        sp.big_entries[1] += sp.lo_stats[1];
-        sp.remap.lo = LOW_CUT_BIN0;
-        sp.remap.hi = LOW_CUT_BIN1;
-        sp.remap.to = to;
-        sp.remap.thin_bin = THIN_BIN;
-        sp.remap.nthin = nthin;
-        big = LOW_CUT_FLOPS;
-      }
-    }
-    work[CBG_WORK_BIG_CUT] = big;
-    bin_scatter(nz, sp, sb, s, df);
-    big_entries = (int64_t)sp.big_entries[0];
-    thin_entries = (int64_t)sp.big_entries[1];
-  }
-  // small-column symbolic bins on the side stream, big columns on the main one
-  // (bins 1..SYM_FUSED_LAST fused with their numeric)
-  DBuf<int32_t> fused_ir;
-  DBuf<double> fused_val;
-  DBuf<int64_t> fused_slot;  // temporary slot of each fused column (-1: none)
-  size_t fused_off[SYM_FUSED_LAST + 2] = {};  // temporary slots of the fused bins 1..SYM_FUSED_LAST
-  // slot width of fused bin b: its flops bound (big >= 64 never clips bins 1..6,
-  // and a clipped bin 7 .. 9 holds columns of <= big flops)
-  auto fmax_of = [&](int b) { return (int)kSymThr[b]; };
-  if (fused) {
-    fused_slot.reset(nz);
-    CBG_HIP(hipMemsetAsync(fused_slot.p, 0xff, sizeof(int64_t) * nz, s));  // -1: not fused (before the fork)
-  }
-  // inline records of A's columns for the small-column and thin passes when A's
-  // columns are short (<= 2 entries on average) and each entry is gathered many
-  // times (flops >= 4 nnz(A)): GalerkinNew's S*(AT), S = T^T
-  DBuf<int4> ainl;
-  {
-    unsigned long long fsmall = 0;
-    for (int b = 1; b < NSMALL; ++b) fsmall += sb.flops[b];
-    fsmall += thin_R ? sb.flops[THIN_BIN] : 0;
-    if (fused && A.nnz <= 2 * A.nzc && (double)fsmall >= 4.0 * (double)A.nnz) {
-      ainl.reset(2 * (A.n + 1));
-      hipLaunchKernelGGL(k_inline_cols, dim3(nblk(A.n + 1, 256)), dim3(256), 0, s, A.n + 1, cmap.p, A.ir, A.val,
-                         ainl.p);
-    }
-  }
-  fork(s);
-  // streams of the small symbolic bins (balance_bins; the fused bins also do
-  // their numeric work: cost 2 per flop)
-  hipStream_t symst[NSMALL];
-  bool big_dominant = false;  // the (column, panel) units carry most of the flops over >= 8 row panels
-  {
-    double main_w = 0.0;
-    for (int b = NSMALL; b < NSMALL + NGCLS; ++b) main_w += (double)sb.flops[b];
-    double cost[NSMALL];
-    for (int b = 0; b < NSMALL; ++b) cost[b] = (fused && b >= 1 && b <= SYM_FUSED_LAST) ? 2.0 : 1.0;
-    // The small symbolic bins join the main stream, ahead of
-    // the (column, panel) units, when those carry most of the flops over >= 8
-    // row panels -- on the side stream they co-ran with k_sym_panel for its
-    // whole length and slowed it (scale 22: 436.3 vs 443.1 ms, scale 24:
-    // 3948 vs 3965 ms); small products (scale 18: R = 1) and small-column
-    // products (GalerkinNew) keep the concurrency (side: 6.67 vs 6.79 ms and
-    // 6.37 vs 6.85 ms)
-    hipStream_t sy = ssym;
-    if (bp.R >= 8) {
-      double small_w = 0.0;
-      for (int b = 1; b < NSMALL; ++b) small_w += (double)sb.flops[b];
-      big_dominant = main_w >= small_w;
-    }
-    if (big_dominant) sy = s;
-    symst[0] = sy;
-    balance_bins(sb.flops, 1, NSMALL - 1, main_w, 0.0, cost, s, sy, symst, !big_dominant);
-  }
-  {
-    const int32_t* P = sb.perm.p;
-    auto at = [&](int b) { return P + sb.offset[b]; };
-    if (fused) {
-      // bins 1..SYM_FUSED_LAST (flops <= 512): symbolic and numeric in one pass into fused_ir/val
-      for (int b = 1; b <= SYM_FUSED_LAST; ++b)
-        fused_off[b + 1] = fused_off[b] + (size_t)sb.count[b] * (size_t)fmax_of(b);
-      // the thin columns' unique entries follow the fused bins' slots
-      const size_t ftot = fused_off[SYM_FUSED_LAST + 1] + (thin_R ? (size_t)sb.flops[THIN_BIN] : 0);
-      fused_ir.reset(ftot + 1);
-      fused_val.reset(ftot + 1);
-      for (int b = 1; b <= SYM_FUSED_LAST; ++b) {
-        if (semiring == CBG_MIN_PLUS)
-          launch_esc<1>(at(b), sb.count[b], fmax_of(b), B, cmap.p, ainl.p, A, cnt.p, fused_ir.p, fused_val.p,
-                        (int64_t)fused_off[b], fused_slot.p, symst[b]);
-        else
-          launch_esc<0>(at(b), sb.count[b], fmax_of(b), B, cmap.p, ainl.p, A, cnt.p, fused_ir.p, fused_val.p,
-                        (int64_t)fused_off[b], fused_slot.p, symst[b]);
-      }
-    }
-    static_assert(SYM_FUSED_LAST == 8 || SYM_FUSED_LAST == 9, "fused bins");
-    if (SYM_FUSED_LAST < 9) launch_sym_wave<10>(at(9), sb.count[9], B, cmap.p, A, cnt.p, symst[9]);
-    launch_sym_block<11, 256>(at(10), sb.count[10], B, cmap.p, ainl.p, A, cnt.p, symst[10]);
-    launch_sym_block<12, 256>(at(11), sb.count[11], B, cmap.p, ainl.p, A, cnt.p, symst[11]);
-    launch_sym_block<13, 512>(at(12), sb.count[12], B, cmap.p, ainl.p, A, cnt.p, symst[12]);
-  }
-  bp.nbig = sb.offset[NSMALL + NGCLS] - sb.offset[NSMALL];
-  bp.perm_big = sb.perm.p + sb.offset[NSMALL];
-  const int nbig = bp.nbig;
-  const int64_t nbr = (int64_t)nbig * bp.R;
-  // f32 copy of A's values for the slab kernels (checked once per A; the
-  // verdict is read back with host sync 2)
-  DBuf<float> valf_own;
-  DBuf<float>& valf = ap.active ? ap.valf : valf_own;
-  DBuf<PackedRV> valp_own;
-  DBuf<PackedRV>& valp = ap.active ? ap.valp : valp_own;
-  DBuf<PackedRVD> valpd_own;
-  int af = ap.active ? ap.af : -1, af_inexact = 0;
-  int ai = ap.active ? ap.ai : -1, amax = ap.active ? ap.amax : 0;
-  DBuf<int> af_flag;
-  // [0] A not f32-exact | [1] A not integral, [2] max |a| | [4] B not integral,
-  // [5] max |b|, [6] B's largest column |sum| (IACC; read with sync 2)
-  int* afh = reinterpret_cast<int*>(host_stage(STAGE_AF));
-  if (nbig > 0 && af < 0 && !sym_only) {
-    valf.reset(A.nnz);
-    valp.reset(A.nnz);
-    af_flag.reset(4);  // ([3]: k_int_bound's unused column-sum slot)
-    CBG_HIP(hipMemsetAsync(af_flag.p, 0, 4 * sizeof(int), s));
-    const int64_t nb = std::min<int64_t>(nblk(A.nnz, 256), (int64_t)device_cus() * 16);
-    hipLaunchKernelGGL(k_vals_f32, dim3((unsigned)nb), dim3(256), 0, s, A.nnz, A.val, valf.p, af_flag.p, A.ir,
-                       valp.p);
-    hipLaunchKernelGGL(k_int_bound, dim3((unsigned)nb), dim3(256), 0, s, A.nnz, A.val, af_flag.p + 1, af_flag.p);
-    CBG_HIP(hipMemcpyAsync(afh, af_flag.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-  }
-  DBuf<int> bint;
-  afh[4] = 1;  // (no check: not integral)
-  if (nbig > 0 && !sym_only && af != 0 && ai != 0) {
-    bint.reset(3);
-    CBG_HIP(hipMemsetAsync(bint.p, 0, 3 * sizeof(int), s));
-    hipLaunchKernelGGL(k_col_int_bound, dim3((unsigned)std::min<int64_t>(nblk(B.nzc * WAVE, 256), (int64_t)device_cus() * 8)),
-                       dim3(256), 0, s, B.nzc, B.cp, B.val, bint.p, af_flag.p);
-    CBG_HIP(hipMemcpyAsync(afh + 4, bint.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-  }
-  if (nbig > 0) {
-    // panel column maps of A (reused across phases like cmap)
-    constexpr int pm_entries = 64;  // map only the referenced A columns when big-column entries * 64 < A's columns
-    bp.n1 = A.n + 1;
-    // column-major panel maps for the symbolic's XCD column order: a column's R
-    // entries in one or two lines (scale 22: 399.6 -> 395.5 ms alone, with the
-    // order 384 ms; the numeric slabs, panel-major, read them at the same speed)
-    bp.kmajor = bp.R > 1;
-    if (ap.active && ap.cmapP.p && ap.plog == bp.plog && ap.kmajor == bp.kmajor) {
-      bp.cmapP = ap.cmapP.p;
-    } else if (bp.R > 1 && pm_entries > 0 && big_entries * pm_entries < A.nzc) {
-      // few big-column entries (GalerkinNew's A*T: ~10^3 of A's 4 M columns;
-      // not the phase plan's sample of scale 22, 1/10 of them, whose hub
-      // references would each search their long A column again):
-      // map only the A columns they reference, without the memset of the
-      // R x n map; this B's own map, never cached for other pieces / phases
-      bp.cmapP_own.reset((size_t)bp.R * (A.n + 1));
-      hipLaunchKernelGGL(k_colmap_panels_entries, dim3(nblk((int64_t)nbig * WAVE, 256)), dim3(256), 0, s,
-                         bp.perm_big, nbig, B.cp, B.ir, cmap.p, A.ir, bp.plog, bp.R, bp.pm().sr, bp.pm().sk,
-                         bp.cmapP_own.p);
-      bp.cmapP = bp.cmapP_own.p;
-    } else {
-      DBuf<int2>& cp = ap.active ? ap.cmapP : bp.cmapP_own;
-      cp.reset((size_t)bp.R * (A.n + 1));
-      if (bp.R == 1) {
-        hipLaunchKernelGGL(k_colmap_panel1, dim3(nblk(A.n + 1, 256)), dim3(256), 0, s, A.n + 1, cmap.p, cp.p);
-      } else {
-        CBG_HIP(hipMemsetAsync(cp.p, 0, sizeof(int2) * bp.R * (A.n + 1), s));
-        hipLaunchKernelGGL(k_colmap_panels_col, dim3(nblk(A.nzc, 256)), dim3(256), 0, s, A.nzc, A.cp, A.jc, A.ir,
-                           bp.plog, bp.R, bp.pm().sr, bp.pm().sk, cp.p);
-      }
-      if (ap.active) {
-        ap.plog = bp.plog;
-        ap.kmajor = bp.kmajor;
-      }
-      bp.cmapP = cp.p;
-    }
-    bp.desc.reset((size_t)nbr * NFINE_MAX);
-    bp.nslab.reset(nbr);
-    bp.cnt_br.reset(nbr);
-    // keep the symbolic bitmaps for the numeric phase when they fit a budget
-    // (saves the numeric marking pass); otherwise numeric rebuilds them
-    // slots are handed out in launch order by the bitmap-mode pairs
-    const int64_t slot_bytes = (int64_t)4 << (bp.plog - 5);
-    const int64_t nslots = sym_only ? 0 : std::min<int64_t>(nbr, (int64_t)(bitmap_budget_bytes() / slot_bytes));
-    DBuf<int> gbm_next;
-    if (nslots > 0) {
-      bp.gbm.reset((size_t)nslots << (bp.plog - 5));
-      bp.gbm_slot.reset(nbr);
-      gbm_next.reset(1);
-      CBG_HIP(hipMemsetAsync(gbm_next.p, 0, sizeof(int), s));
-    }
-    if (nbr >= (int64_t)INT32_MAX) throw HipError("too many (column, panel) pairs", CBG_ERR_NOTSUPPORTED);
-    // the multi-slab pairs' cut positions, handed out by an atomic counter up to
-    // a budget (pairs past it leave their cuts to the numeric's searches)
-    DBuf<unsigned long long> cuts_next;
-    long long cuts_cap = 0;
-    if (!sym_only) {
-      // at most min(1.5 GB, 2 % of the free HBM), and never more than the cuts of
-      // every pair cut into NFINE_MAX slabs (GalerkinNew's few big columns need
-      // little); CBG_CUTS_CAP (entries, read per call) is a test hook that leaves
-      // pairs past it to the numeric's searches
-      cuts_cap = std::min<long long>(INT32_MAX, (long long)(std::min(1.5e9, 0.02 * device_bytes_available()) / 4));
-      cuts_cap = std::min<long long>(cuts_cap, (long long)big_entries * bp.R * (NFINE_MAX - 1));
-      if (const char* e = getenv("CBG_CUTS_CAP")) cuts_cap = std::min<long long>(cuts_cap, atoll(e));
-      bp.cuts.reset(std::max<long long>(cuts_cap, 1));
-      bp.pcoff.reset(nbr);
-      cuts_next.reset(1);
-      CBG_HIP(hipMemsetAsync(bp.pcoff.p, 0xff, sizeof(int) * nbr, s));
-      CBG_HIP(hipMemsetAsync(cuts_next.p, 0, sizeof(unsigned long long), s));
-    }
-    const int pwords = 1 << (bp.plog - 5);
-    auto lds_of = [&](int hw) {
-      return (size_t)hw * 4 + NFINE_MAX * 4 + (BIG_BS + 4) * 4 + BIG_BS * 4 + (BIG_BS / WAVE + 4) * 4 +
-             (size_t)SYM_OVF_CAP * 4;
-    };
-    set_lds(k_sym_panel<true>, lds_of(std::max(pwords, GROUP_T)));
-    set_lds(k_sym_panel<false>, lds_of(std::max(pwords, GROUP_T)));
-    SymPanelArgs sa{bp.perm_big, bp.R, bp.plog, 0, 0, pwords, 0, B.cp, B.ir, bp.pm(), A.ir, A.m,
-                    cnt.p, bp.cnt_br.p, bp.desc.p, bp.nslab.p, bp.gbm.p, (int)nslots, gbm_next.p,
-                    bp.gbm_slot.p,
-                    bp.cuts.p, cuts_next.p, cuts_cap,
-                    bp.pcoff.p, nullptr, nullptr};
-    // group units that overflow one hash slab, collected for k_sym_deferred
-    int64_t group_units = 0;
-    for (int c = 0; c < NGCLS; ++c)
-      if (GROUP_LOG_MAX - c > 0)
-        group_units += (int64_t)sb.count[NSMALL + c] * ((bp.R + (1 << (GROUP_LOG_MAX - c)) - 1) >> (GROUP_LOG_MAX - c));
-    DBuf<int4> defer;
-    DBuf<int> defer_n;
-    if (group_units > 0) {
-      defer.reset(group_units);
-      defer_n.reset(1);
-      CBG_HIP(hipMemsetAsync(defer_n.p, 0, sizeof(int), s));
-      sa.defer = defer.p;
-      sa.defer_n = defer_n.p;
-    }
-    // one launch per group class (largest groups first)
-    for (int c = 0; c < NGCLS; ++c) {
-      const int nc = sb.count[NSMALL + c];
-      if (nc == 0) continue;
-      sa.glog = GROUP_LOG_MAX - c;
-      sa.boff = sb.offset[NSMALL + c] - sb.offset[NSMALL];
-      sa.hwords = sa.glog > 0 ? std::max(pwords, GROUP_T) : pwords;
-      const int64_t RG = (bp.R + (1 << sa.glog) - 1) >> sa.glog;
-      sa.ncls = nc;
-      work[sa.glog > 0 ? CBG_WORK_SYM_GROUP_UNITS : CBG_WORK_SYM_PANEL_UNITS] += RG * nc;
-      // resident blocks per CU at this launch's LDS size
-      const int per_cu = sa.glog > 0 ? blocks_per_cu(k_sym_panel<true>, BIG_BS, lds_of(sa.hwords))
-                                     : blocks_per_cu(k_sym_panel<false>, BIG_BS, lds_of(sa.hwords));
-      // (a multiple of 8: the XCD column order; 8 x ceil(nc / 8) x RG units)
-      const int64_t grid = std::min<int64_t>(RG * ((nc + 7) / 8) * 8,
-                                             ((int64_t)per_cu * device_cus() * CBG_SYM_WAVES_OF_UNITS) & ~7LL);
-      if (sa.glog > 0)
-        hipLaunchKernelGGL(k_sym_panel<true>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
-      else
-        hipLaunchKernelGGL(k_sym_panel<false>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
-    }
-    if (group_units > 0) {
-      sa.hwords = std::max(pwords, GROUP_T);
-      set_lds(k_sym_deferred, lds_of(sa.hwords));
-      hipLaunchKernelGGL(k_sym_deferred, dim3((unsigned)std::min<int64_t>(group_units, device_cus() * 4)),
-                         dim3(BIG_BS), lds_of(sa.hwords), s, sa);
-      CBG_HIP(hipMemcpyAsync(reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS)) + 5, defer_n.p, sizeof(int),
-                             hipMemcpyDeviceToHost, s));
-      df.take(defer);
-      df.take(defer_n);
-    }
-    // the symbolic kernels may still run: the counters stay allocated until the
-    // multiply's last synchronization
-    bp.gbm_next = gbm_next.p;
-    bp.gbm_slots = nslots;
-    df.take(gbm_next);
-    df.take(cuts_next);
-  }
-  // the thin columns' sort after the big columns' launches (its host
-  // synchronizations would otherwise hold them back)
-  {
-    // CBG_DBG bit 16: the symbolic bins' sizes
-    static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
-    if (dbg & 16) {
-      unsigned long long fs = 0, fh = 0, fb = 0;
-      for (int b = 1; b <= SYM_FUSED_LAST; ++b) fs += sb.flops[b];
-      for (int b = SYM_FUSED_LAST + 1; b < NSMALL; ++b) fh += sb.flops[b];
-      for (int b = NSMALL; b < NSMALL + NGCLS; ++b) fb += sb.flops[b];
-      std::fprintf(stderr,
-                   "[cbg bins] fused cols %d flops %llu | hash cols %d flops %llu | big cols %d flops %llu | "
-                   "thin cols %d entries %lld flops %llu | inline A %d\n",
-                   sb.offset[SYM_FUSED_LAST + 1] - sb.offset[1], fs, sb.offset[NSMALL] - sb.offset[SYM_FUSED_LAST + 1],
-                   fh, nbig, fb, thin_R ? sb.count[THIN_BIN] : 0, (long long)thin_entries,
-                   thin_R ? (unsigned long long)sb.flops[THIN_BIN] : 0ull, ainl.p != nullptr);
-    }
-  }
-  if (thin_R && sb.count[THIN_BIN] > 0) {
-    // on the copy stream (idle until the numeric), from the fork point, so the
-    // sort runs beside the small-column bins of both streams instead of behind
-    // the main stream's (its readback then waits for the sort alone)
-    CBG_HIP(hipStreamWaitEvent(scopy, ev_fork, 0));
-    thin_columns(sb.perm.p + sb.offset[THIN_BIN], sb.count[THIN_BIN], thin_entries, (int64_t)sb.flops[THIN_BIN], A,
-                 B, cmap.p, ainl.p, semiring, cnt.p, fused_slot.p, fused_ir.p, fused_val.p,
-                 (int64_t)fused_off[SYM_FUSED_LAST + 1], scopy, df);
-    CBG_HIP(hipEventRecord(ev_cjoin, scopy));
-    CBG_HIP(hipStreamWaitEvent(s, ev_cjoin, 0));
-  }
-  join(s);
-  // Everything that depends only on the per-column counts is launched now and
-  // read back in ONE synchronization: nnz(C) (column pointers), the number of
-  // slabs, the numeric bins' histogram and the number of nonempty C columns.
-  DBuf<int64_t> colptr(nz + 1);
-  exclusive_scan_i32_to_i64(cnt.p, colptr.p, nz, s, &df);
-  // nnz(C), slabs, nonempty C columns, flops: one pinned slot, read after sync 2
-  int64_t* scal = reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS));
-  scal[1] = 0;
-  CBG_HIP(hipMemcpyAsync(&scal[0], colptr.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  // slab lists of big columns
-  DBuf<int64_t> sbase;
-  DBuf<SlabRec> slist;
-  int64_t nslabs = 0;
-  if (nbig > 0) {
-    sbase.reset(nbr + 1);
-    exclusive_scan_i32_to_i64(bp.nslab.p, sbase.p, nbr, s, &df);
-    CBG_HIP(hipMemcpyAsync(&scal[1], sbase.p + nbr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  }
-  BinPending npend;
-  bin_classify(nz, flops.p, cnt.p, 1, kNumThr, 9, big, npend, s, fused ? kSymThr[SYM_FUSED_LAST] : 0, B.cp,
-               MAXBINS, thin_R, 0, copy1);
-  // compaction of C's columns (SpDCCols(SpTuples): nonempty columns only)
-  DBuf<int64_t> flag(nz + 1), pos(nz + 1);
-  hipLaunchKernelGGL(k_col_flags, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, cnt.p, flag.p);
-  exclusive_scan_i64(flag.p, pos.p, nz, s, &df);
-  CBG_HIP(hipMemcpyAsync(&scal[2], pos.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipMemcpyAsync(&scal[3], flops.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  // single-entry big columns: their sizes' scan (the chunked copy), total read back with sync 2
-  DBuf<int64_t> sb_sz, sb_off;
-  scal[4] = 0;
-  if (copy1 > 1 && !sym_only) {
-    sb_sz.reset(nz);
-    sb_off.reset(nz + 1);
-    hipLaunchKernelGGL(k_single_big_sizes, dim3(nblk(nz, 256)), dim3(256), 0, s, nz, B.cp, flops.p, big, sb_sz.p);
-    exclusive_scan_i64(sb_sz.p, sb_off.p, nz, s, &df);
-    CBG_HIP(hipMemcpyAsync(&scal[4], sb_off.p + nz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  }
-  CBG_HIP(hipEventRecord(ev1, s));
-  CBG_HIP(hipStreamSynchronize(s));  // host sync 2 of 4
-  const int64_t nnzc = scal[0], nzcC = scal[2], flops_total = scal[3];
-  nslabs = scal[1];
-  const int64_t single_big_entries = scal[4];
-  work[CBG_WORK_SYM_DEFERRED_UNITS] = scal[5];
-  for (int b = 1; fused && b <= SYM_FUSED_LAST; ++b) work[CBG_WORK_ESC_COLUMNS] += sb.count[b];
-  work[CBG_WORK_THIN_COLUMNS] = thin_R ? sb.count[THIN_BIN] : 0;
-  work[CBG_WORK_SINGLE_BIG_ENTRIES] = copy1 > 1 ? single_big_entries : 0;
-  if (sym_only) {
-    df.synced = true;
-    if (st) {
-      float a = 0;
-      CBG_HIP(hipEventElapsedTime(&a, ev0, ev1));
-      *st = LocalStats{};
-      st->ms_symbolic = a;
-      st->nnz = nnzc;
-      st->n_big = nbig;
-      st->flops = flops_total;
-      std::memcpy(st->work, work, sizeof(work));
-    }
-    return;
-  }
-  if (af_flag.p) {
-    af_inexact = afh[0];
-    af = af_inexact ? 0 : 1;
-    ai = afh[1] ? 0 : 1;
-    amax = afh[2];
-    if (ap.active) {
-      ap.af = af;
-      ap.ai = ai;
-      ap.amax = amax;
-    }
-    if (!af) {
-      valf.release();
-      valp.release();
-    }
-  }
-  if (af == 1) bp.valAf = valf.p;
-  if (af == 1 && valp.p) bp.valAp = valp.p;
-  uint64_t big_fl = 0;
-  for (int b = NSMALL; b < NSMALL + NGCLS; ++b) big_fl += sb.flops[b];
-  DBuf<PackedRVD>& vd = ap.active ? ap.valpd : valpd_own;
-  if (af == 0 && nbig > 0 && (vd.p || big_fl >= 4 * (uint64_t)A.nnz)) {
-    // the f64-valued slab path reads A as (row, f64) records (built once per A,
-    // when the big columns' products are enough to pay for its 24 B per entry:
-    // GalerkinNew scale 22 packed 68 M entries, 0.34 ms, for 3.7 M products)
-    if (!vd.p) {
-      vd.reset(A.nnz);
-      hipLaunchKernelGGL(k_pack_rvd, dim3((unsigned)std::min<int64_t>(nblk(A.nnz, 256), (int64_t)device_cus() * 16)),
-                         dim3(256), 0, s, A.nnz, A.ir, A.val, vd.p);
-    }
-    bp.valAd = vd.p;
-  }
-  bp.iacc = bp.valAp && ai == 1 && !afh[4] && iacc_bound_ok(semiring, amax, afh[5], afh[6]);
-  work[CBG_WORK_IACC] = bp.iacc ? 1 : 0;
-  {
-    // test hook (CBG_FAULT_C_BYTES, read per call): C larger than this fails as
-    // an out-of-memory would, after the symbolic pass -- the phase splitting of
-    // MemEfficientSpGEMM (cbg_summa.cpp multiply_to_fn) is tested with it
-    const char* e = getenv("CBG_FAULT_C_BYTES");
-    if (e && 12.0 * (double)nnzc > atof(e)) {
-      df.synced = true;
-      throw HipError("C of " + std::to_string(nnzc) + " entries exceeds CBG_FAULT_C_BYTES", CBG_ERR_OOM);
-    }
-  }
-  C.nzc = nzcC;
-  C.cp = static_cast<int64_t*>(pool().alloc(sizeof(int64_t) * (nzcC + 1)));
-  C.jc = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(nzcC, 1)));
-  Cg.t = C;
-  hipLaunchKernelGGL(k_col_scatter, dim3(nblk(nz + 1, 256)), dim3(256), 0, s, nz, cnt.p, pos.p, B.jc, colptr.p, C.jc,
-                     C.cp);
-  int ncls[SLAB_NCLS] = {};
-  if (nbig > 0 && nslabs > 0) {
-    slist.reset(nslabs);
-    const int NK = SLAB_NCLS * slab_kr(bp.R);
-    DBuf<int> counters(2 * NK + SLAB_NCLS);  // counts[NK] | cursor[NK] | class totals
-    CBG_HIP(hipMemsetAsync(counters.p, 0, (2 * NK + SLAB_NCLS) * sizeof(int), s));
-    const int rank_span = 1 << bp.plog, rank_min = RANK_SLABS_MIN;
-    // (CBG_GRANK_MIN, read per call: group slabs of more nonzeros than this run
-    // as group rank slabs; -1 none)
-    const char* egm = getenv("CBG_GRANK_MIN");
-    const int grank_min = egm ? (atoi(egm) < 0 ? INT32_MAX : atoi(egm)) : GRANK_SLABS_MIN;
-    hipLaunchKernelGGL(k_slab_count, dim3(nblk(nbig, 256)), dim3(256), NK * sizeof(int), s, nbig, bp.R, bp.nslab.p,
-                       bp.cnt_br.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p);
-    hipLaunchKernelGGL(k_slab_bases, dim3(1), dim3(64), 0, s, bp.R, counters.p, counters.p + NK,
-                       counters.p + 2 * NK);
-    hipLaunchKernelGGL(k_slab_fill, dim3(nblk(nbig, 256)), dim3(256), 2 * NK * sizeof(int), s, nbig, bp.R,
-                       bp.nslab.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p + NK, slist.p,
-                       bp.perm_big, B.cp, colptr.p,
-                       bp.gbm_slot.p, bp.plog, A.m, bp.pcoff.p);
-    int* ncls_h = reinterpret_cast<int*>(host_stage(STAGE_SLABS));
-    CBG_HIP(hipMemcpyAsync(ncls_h, counters.p + 2 * NK, SLAB_NCLS * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (bp.gbm_next)
-      CBG_HIP(hipMemcpyAsync(ncls_h + SLAB_NCLS, bp.gbm_next, sizeof(int), hipMemcpyDeviceToHost, s));
-    CBG_HIP(hipStreamSynchronize(s));  // host sync 3 of 4: the slab classes' sizes
-    std::memcpy(ncls, ncls_h, sizeof(int) * SLAB_NCLS);
-    // (CBG_DBG bit 128 hands out slots without storing the bitmaps: the
-    // marking pass must run)
-    static const int dbg_kept = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
-    bp.all_kept = bp.gbm_next && (int64_t)ncls_h[SLAB_NCLS] <= bp.gbm_slots && !(dbg_kept & 128);
-    df.take(counters);
-    work[bp.all_kept ? CBG_WORK_BITMAP_SMALL_KEPT : CBG_WORK_BITMAP_SMALL_MARK] = ncls[0];
-    work[bp.all_kept ? CBG_WORK_BITMAP_LARGE_KEPT : CBG_WORK_BITMAP_LARGE_MARK] = ncls[1];
-    for (int k = 0; k < SLAB_HASH_NCLS; ++k) work[CBG_WORK_HASH0 + k] = ncls[2 + k];
-    for (int k = 0; k < SLAB_RANK_NCLS; ++k) work[CBG_WORK_RANK0 + k] = ncls[SLAB_RANK0 + k];
-    for (int k = 0; k < SLAB_GRANK_NCLS; ++k) work[CBG_WORK_GRANK0 + k] = ncls[SLAB_GRANK0 + k];
-    static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
-    if (dbg & 16)
-    {
-      static const int ht[SLAB_HASH_NCLS] = {CBG_HASH_TABLES};
-      std::fprintf(stderr, "[cbg slabs] bitmap small %d large %d | hash", ncls[0], ncls[1]);
-      for (int k = 0; k < SLAB_HASH_NCLS; ++k) std::fprintf(stderr, " T%d %d", ht[k], ncls[2 + k]);
-      std::fprintf(stderr, " | rank N1024 %d N2048 %d N4096 %d | group rank N2048 %d N4096 %d", ncls[SLAB_RANK0],
-                   ncls[SLAB_RANK0 + 1], ncls[SLAB_RANK0 + 2], ncls[SLAB_GRANK0], ncls[SLAB_GRANK0 + 1]);
-      std::fprintf(stderr, "\n");
-    }
-  }
-  // output arrays
-  C.nnz = nnzc;
-  if (sink) {
-    sink->place(nnzc, &C.ir, &C.val);
-    C.reserved |= TILE_BORROWED_ENTRIES;
-  } else {
-    C.ir = static_cast<int32_t*>(pool().alloc(sizeof(int32_t) * std::max<int64_t>(nnzc, 1)));
-    C.val = static_cast<double*>(pool().alloc(sizeof(double) * std::max<int64_t>(nnzc, 1)));
-  }
-  Cg.t = C;
-  // numeric
-  Binned nbn;
-  bin_scatter(nz, npend, nbn, s, df);
-  for (int b = 1; b <= 4; ++b) work[CBG_WORK_WAVE_BIN_COLUMNS] += nbn.count[b];
-  for (int b = 5; b <= 8; ++b) work[CBG_WORK_HASH_BIN_COLUMNS] += nbn.count[b];
-  // small-column bins on the side stream, big-column slabs on the main one,
-  // the copies (fused bins, single-entry columns) on the copy stream: they only
-  // need colptr and stream at HBM rate beside the latency-bound kernels
-  // (GalerkinNew at 22: 5.92 / 5.98 vs 6.45 / 6.38 ms); not where the big
-  // columns' slabs dominate, which they slow (scale 22: 418.4 vs 413.0 ms)
-  const bool copy_stream = !big_dominant;
-  fork(s);
-  const hipStream_t sc = copy_stream ? scopy : snum;
-  if (copy_stream) CBG_HIP(hipStreamWaitEvent(scopy, ev_fork, 0));
-  hipStream_t numst[10];
-  {
-    // the slabs of the big columns on the main stream; the fused bins' copies on
-    // the side one (about a quarter of a product's cost per entry)
-    double fused_w = 0.0;
-    if (fused && !copy_stream)
-      for (int b = 1; b <= SYM_FUSED_LAST; ++b) fused_w += 0.25 * (double)sb.flops[b];
-    numst[0] = numst[9] = snum;
-    // balanced when the copies have their own stream (GalerkinNew 6.01 vs 6.07 ms,
-    // 3 rounds; round 3, before the copy stream: 9.9-10.2 vs 10.0 ms, off)
-    balance_bins(nbn.flops, 1, 8, (double)nbn.flops[9], fused_w, nullptr, s, snum, numst, copy_stream);
-  }
-  // (the whole-column bins on the side stream overlap the slabs: serialized after
-  // them on the main stream they take ~13 ms per scale-22 step and the step is
-  // 1 ms longer, before them 0.6 ms longer -- profiles/r06_ab_numbins.json)
-  if (semiring == CBG_MIN_PLUS) numeric_dispatch<1>(nbn, A, bp.valAf, B, cmap.p, ainl.p, colptr.p, C, numst, df);
-  else numeric_dispatch<0>(nbn, A, bp.valAf, B, cmap.p, ainl.p, colptr.p, C, numst, df);
-  if (fused && (fused_off[SYM_FUSED_LAST + 1] > 0 || (thin_R && sb.count[THIN_BIN] > 0)))
-  {
-    hipLaunchKernelGGL(k_copy_fused, dim3(nblk(nz, 256)), dim3(256), 0, sc, nz, fused_slot.p, cnt.p,
-                       colptr.p, fused_ir.p, fused_val.p, C.ir, C.val, (int64_t)fused_off[SYM_FUSED_LAST + 1]);
-    if (thin_R)
-      thin_copy(sb.perm.p + sb.offset[THIN_BIN], sb.count[THIN_BIN], fused_slot.p, cnt.p, colptr.p, fused_ir.p,
-                fused_val.p, C.ir, C.val, s);
-  }
-  if (copy1) {
-    if (semiring == CBG_MIN_PLUS)
-      hipLaunchKernelGGL(k_copy_single<1>, dim3(nblk(nz, 256)), dim3(256), 0, sc, nz, B.cp, B.ir, B.val, cmap.p,
-                         flops.p, big, A.ir, A.val, colptr.p, C.ir, C.val);
-    else
-      hipLaunchKernelGGL(k_copy_single<0>, dim3(nblk(nz, 256)), dim3(256), 0, sc, nz, B.cp, B.ir, B.val, cmap.p,
-                         flops.p, big, A.ir, A.val, colptr.p, C.ir, C.val);
-  }
-  if (copy1 > 1 && single_big_entries > 0) {
-    const int ch = (int)std::min<int64_t>(SB_CHUNK, big + 1);
-    const unsigned g = (unsigned)((single_big_entries + ch - 1) / ch);
-    if (semiring == CBG_MIN_PLUS)
-      hipLaunchKernelGGL(k_copy_single_big<1>, dim3(g), dim3(256), 0, sc, nz, sb_off.p, ch, B.cp, B.ir, B.val,
-                         cmap.p, A.ir, A.val, colptr.p, C.ir, C.val);
-    else
-      hipLaunchKernelGGL(k_copy_single_big<0>, dim3(g), dim3(256), 0, sc, nz, sb_off.p, ch, B.cp, B.ir, B.val,
-                         cmap.p, A.ir, A.val, colptr.p, C.ir, C.val);
-  }
-  if (nslabs > 0) {
-    if (semiring == CBG_MIN_PLUS) launch_slabs<1>(slist.p, ncls, bp, A, B, C, s, side, df);
-    else launch_slabs<0>(slist.p, ncls, bp, A, B, C, s, side, df);
-  }
-  join(s);
-  if (copy_stream) {
-    CBG_HIP(hipEventRecord(ev_cjoin, scopy));
-    CBG_HIP(hipStreamWaitEvent(s, ev_cjoin, 0));
-  }
-  CBG_HIP(hipEventRecord(ev2, s));
-  CBG_HIP(hipStreamSynchronize(s));  // host sync 4 of 4: C complete
-  df.synced = true;
-  CBG_HIP(hipGetLastError());
-  {
-    static const int dbg = getenv("CBG_DBG") ? atoi(getenv("CBG_DBG")) : 0;
-    if (dbg & 16) {
-      if (dbg & 32) {
-        unsigned long long gs[16];
-        CBG_HIP(hipMemcpyFromSymbol(gs, HIP_SYMBOL(g_stat), sizeof(gs)));
-        std::fprintf(stderr, "[cbg k_num_slab] slabs %llu nonfull %llu nb %llu nb_nonfull %llu nout %llu multichunk %llu "
-                     "products %llu | hash products panel %llu column %llu nout %llu | rank products %llu nout %llu"
-                     " | symbolic groups %llu products %llu, by panels %llu products %llu\n",
-                     gs[0], gs[1], gs[2], gs[3], gs[5], gs[6], gs[4], gs[7], gs[8], gs[9], gs[10], gs[11], gs[12], gs[13],
-                     gs[14], gs[15]);
-        std::memset(gs, 0, sizeof(gs));
-        CBG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_stat), gs, sizeof(gs)));
-      }
-      unsigned long long ph[24];
-      CBG_HIP(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_phase), sizeof(ph)));
-      const char* names[7] = {"init", "staging", "-", "rankscan", "pass0", "pass1", "output"};
-      std::fprintf(stderr, "[cbg phases, block-us summed / 256 CUs]");
-      for (int k = 0; k < 7; ++k)
-        if (k != 2) std::fprintf(stderr, " %s=%.3fms", names[k], ph[k] / 100.0 / 256.0 / 1000.0);
-      const char* snames[5] = {"sym_staging", "sym_hash", "sym_bitmap_products", "sym_counts_store", "sym_plan"};
-      for (int k = 8; k < 13; ++k) std::fprintf(stderr, " %s=%.3fms", snames[k - 8], ph[k] / 100.0 / 256.0 / 1000.0);
-      const char* hnames[4] = {"hash_clear", "hash_staging", "hash_products", "hash_emit"};
-      const int hk[4] = {7, 13, 14, 15};
-      for (int k = 0; k < 4; ++k) std::fprintf(stderr, " %s=%.3fms", hnames[k], ph[hk[k]] / 100.0 / 256.0 / 1000.0);
-      const char* rnames[5] = {"rank_stage", "rank_products", "rank_scan", "rank_acc", "rank_emit"};
-      for (int k = 0; k < 5; ++k) std::fprintf(stderr, " %s=%.3fms", rnames[k], ph[16 + k] / 100.0 / 256.0 / 1000.0);
-      std::fprintf(stderr, "\n");
-      std::memset(ph, 0, sizeof(ph));
-      CBG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), ph, sizeof(ph)));
-    }
-  }
-  if (st) {
+  prep_a_maps(m);
+  plan_symbolic_bins(m);  // sync 1
+  sym_small_columns(m);
+  check_values(m);
+  sym_big_columns(m);
+  if (dbg_mask() & 16) dbg_report_bins(m);
+  sym_thin_columns(m);
+  scan_counts(m);  // sync 2
+  auto stats = [&](bool numeric_done) {
+    if (!st) return;
     float a = 0, b = 0;
-    CBG_HIP(hipEventElapsedTime(&a, ev0, ev1));
-    CBG_HIP(hipEventElapsedTime(&b, ev1, ev2));
+    CBG_HIP(hipEventElapsedTime(&a, m.ts.ev0, m.ts.ev1));
+    if (numeric_done) CBG_HIP(hipEventElapsedTime(&b, m.ts.ev1, m.ts.ev2));
+    *st = LocalStats{};
     st->ms_symbolic = a;
     st->ms_numeric = b;
-    st->nnz = nnzc;
-    st->n_big = nbig;
-    st->n_slabs = nslabs;
-    st->flops = flops_total;  // total flops (k_flops), read back with sync 2
-    std::memcpy(st->work, work, sizeof(work));
+    st->nnz = m.nnzc;
+    st->n_big = m.bp.nbig;
+    st->n_slabs = numeric_done ? m.nslabs : 0;
+    st->flops = m.flops_total;  // total flops (k_flops), read back with sync 2
+    std::memcpy(st->work, m.work, sizeof(m.work));
+  };
+  if (sym_only) {
+    m.df.synced = true;
+    stats(false);
+    return;
   }
-  Cg.release();  // completed: the caller owns C
+  pick_value_format(m);
+  alloc_c_and_plan_slabs(m);  // sync 3
+  numeric(m);                 // sync 4
+  dbg_report_kernels();
+  stats(true);
+  m.Cg.release();  // completed: the caller owns C
 }
 
 }  // namespace cbg

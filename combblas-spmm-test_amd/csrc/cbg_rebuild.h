@@ -31,9 +31,6 @@
 //
 // Nothing here knows its callers: they differ in their count kernel and in the
 // Emit functor they pass.
-//
-// nblk and set_lds are here, not in cbg_internal.h: cbg_local.hip keeps its own
-// (unclamped) nblk and its set_lds under the same names and does not include this.
 #pragma once
 #include <algorithm>
 
@@ -41,15 +38,6 @@
 #include "cbg_internal.h"
 
 namespace cbg {
-
-// blocks of `per` items that cover n items; at least one (a grid of 0 blocks is refused)
-inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
-template <class K>
-void set_lds(K kernel, size_t bytes) {
-  if (bytes > 65536)
-    CBG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
 
 // ---------------------------------------------------------------------------
 // device pieces
