@@ -82,7 +82,7 @@ EXPORTS = [
     "cbg_grid_transpose", "cbg_grid_block_extract", "cbg_grid_agree", "cbg_merge_stats", "cbg_tile_alloc",
     "cbg_tile_concat_cols", "cbg_device_memory", "cbg_last_summa_info", "cbg_summa_spgemm_memeff",
     "cbg_last_summa_comm",
-    "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_store_probe",
+    "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_local_aprep_bounds", "cbg_store_probe",
     "cbg_tile_col_stats", "cbg_tile_prune_column", "cbg_grid_kselect", "cbg_grid_mcl_prune", "cbg_summa_spgemm_mcl",
     "cbg_mcl_kselect_bounds", "cbg_last_mcl_stats",
     "cbg_grid_reduce_cols", "cbg_mcl_moment_bounds", "cbg_tile_apply", "cbg_grid_make_col_stochastic", "cbg_grid_chaos",
@@ -193,6 +193,7 @@ def lib():
         "cbg_summa_spgemm_mcl": ([vp, T, T, i64, i64, i32, i32, i32, i32, i64, PHASE_FN, vp, T,
                                   ctypes.POINTER(CMclParams)], i32),
         "cbg_mcl_kselect_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_local_aprep_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_mcl_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_grid_reduce_cols": ([vp, T, i32, ctypes.c_double, vp], i32),
         "cbg_mcl_moment_bounds": ([ctypes.POINTER(i64), i32], i32),
@@ -519,7 +520,17 @@ WORK_CLASSES = (["bitmap_small_kept", "bitmap_small_mark", "bitmap_large_kept", 
                 ["rank_N%d" % n for n in (1024, 2048, 4096)] +
                 ["sym_panel_units", "sym_group_units", "sym_deferred_units", "esc_columns", "thin_columns",
                  "single_big_entries", "hash_bin_columns", "wave_bin_columns", "int_accumulate"] +
-                ["group_rank_N%d" % n for n in (2048, 4096)] + ["big_cut_flops"])
+                ["group_rank_N%d" % n for n in (2048, 4096)] + ["big_cut_flops"] +
+                # what each multiply took from / built for the call's cache of A-side preparation
+                ["amap_reused", "pmap_reused", "pmap_built", "pmap_entries", "avals_reused", "rvd_built", "rvd_used"])
+
+
+def local_aprep_bounds():
+    """[entries factor of the private panel map, flops factor of the (row, f64) records]
+    (cbg_local_aprep_bounds)"""
+    b = (ctypes.c_int64 * 2)()
+    n = lib().cbg_local_aprep_bounds(b, 2)
+    return [int(x) for x in b[:n]]
 
 
 def last_work_stats():

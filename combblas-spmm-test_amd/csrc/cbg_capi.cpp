@@ -412,6 +412,8 @@ int cbg_last_work_stats(int64_t* counts, int n) {
   return CBG_WORK_N;
 }
 
+int cbg_local_aprep_bounds(int64_t* bounds, int n) { return cbg::local_aprep_bounds(bounds, n); }
+
 // ---------------- grid ----------------
 int cbg_get_unique_id(void* id);  // cbg_summa_id.cpp
 

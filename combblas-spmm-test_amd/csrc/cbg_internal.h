@@ -258,6 +258,9 @@ struct APrepScope {
   APrepScope() { aprep_begin(); }
   ~APrepScope() { aprep_end(); }
 };
+// the preparation's thresholds (cbg_local_aprep_bounds): the entries factor of the
+// private panel map and the flops factor of the (row, f64) records
+int local_aprep_bounds(int64_t* bounds, int n);
 
 // device exclusive scan of n int64 values -> out[0..n], returns nothing (total at out[n]).
 // df: the scan's temporaries are released with df (no host synchronization);

@@ -3775,6 +3775,18 @@ static APrep& aprep() {
   static thread_local APrep a;
   return a;
 }
+// The preparation's two thresholds (cbg_local_aprep_bounds):
+// a multiply maps only the A columns its big columns reference when their B
+// entries * PMAP_ENTRIES_FACTOR < A's nonempty columns (prep_panel_maps), and
+// the (row, f64) records are packed once the big columns carry at least
+// RVD_FLOPS_FACTOR * nnz(A) flops (pick_value_format)
+constexpr int PMAP_ENTRIES_FACTOR = 64;
+constexpr int RVD_FLOPS_FACTOR = 4;
+int local_aprep_bounds(int64_t* bounds, int n) {
+  const int64_t b[2] = {PMAP_ENTRIES_FACTOR, RVD_FLOPS_FACTOR};
+  for (int i = 0; bounds && i < n && i < 2; ++i) bounds[i] = b[i];
+  return 2;
+}
 void aprep_begin() { aprep().active = true; }
 void aprep_end() {
   aprep().rebind(nullptr, 0, 0);
@@ -3946,6 +3958,7 @@ static void prep_a_maps(LocalMul& m) {
   const uint64_t ser_ir = ap.active ? pool().serial_of(A.ir) : 0, ser_cp = ap.active ? pool().serial_of(A.cp) : 0;
   const bool a_hit = ap.holds(A, ser_ir, ser_cp);
   if (ap.active && !a_hit) ap.rebind(&A, ser_ir, ser_cp);
+  m.work[CBG_WORK_AMAP_REUSED] = a_hit ? 1 : 0;
   if (!a_hit) {
     DBuf<int2>& cmap = m.cmap();
     DBuf<unsigned char>& clen8 = m.clen8();
@@ -4137,6 +4150,7 @@ static void check_values(LocalMul& m) {
   m.ai = m.ap.active ? m.ap.ai : -1;
   m.amax = m.ap.active ? m.ap.amax : 0;
   m.afh = reinterpret_cast<int*>(host_stage(STAGE_AF));
+  m.work[CBG_WORK_AVALS_REUSED] = (nbig > 0 && !m.sym_only && m.af >= 0) ? 1 : 0;
   if (nbig > 0 && m.af < 0 && !m.sym_only) {
     m.valf().reset(A.nnz);
     m.valp().reset(A.nnz);
@@ -4165,7 +4179,8 @@ static void prep_panel_maps(LocalMul& m) {
   const hipStream_t s = m.s;
   APrep& ap = m.ap;
   BigPlan& bp = m.bp;
-  constexpr int pm_entries = 64;  // map only the referenced A columns when big-column entries * 64 < A's columns
+  // map only the referenced A columns when big-column entries * 64 < A's columns
+  constexpr int pm_entries = PMAP_ENTRIES_FACTOR;
   bp.n1 = A.n + 1;
   // column-major panel maps for the symbolic's XCD column order: a column's R
   // entries in one or two lines (scale 22: 399.6 -> 395.5 ms alone, with the
@@ -4173,6 +4188,7 @@ static void prep_panel_maps(LocalMul& m) {
   bp.kmajor = bp.R > 1;
   if (ap.active && ap.cmapP.p && ap.plog == bp.plog && ap.kmajor == bp.kmajor) {
     bp.cmapP = ap.cmapP.p;
+    m.work[CBG_WORK_PMAP_REUSED] = 1;
   } else if (bp.R > 1 && pm_entries > 0 && m.big_entries * pm_entries < A.nzc) {
     // few big-column entries (GalerkinNew's A*T: ~10^3 of A's 4 M columns;
     // not the phase plan's sample of scale 22, 1/10 of them, whose hub
@@ -4184,7 +4200,9 @@ static void prep_panel_maps(LocalMul& m) {
                        bp.perm_big, bp.nbig, B.cp, B.ir, m.cmap().p, A.ir, bp.plog, bp.R, bp.pm().sr, bp.pm().sk,
                        bp.cmapP_own.p);
     bp.cmapP = bp.cmapP_own.p;
+    m.work[CBG_WORK_PMAP_ENTRIES] = 1;
   } else {
+    m.work[CBG_WORK_PMAP_BUILT] = 1;
     DBuf<int2>& cp = ap.active ? ap.cmapP : bp.cmapP_own;
     cp.reset((size_t)bp.R * (A.n + 1));
     if (bp.R == 1) {
@@ -4411,6 +4429,9 @@ static void pick_value_format(LocalMul& m) {
     m.af = af_inexact ? 0 : 1;
     m.ai = m.afh[1] ? 0 : 1;
     m.amax = m.afh[2];
+    // (k_int_bound does not run on an A that is not f32-exact and leaves its
+    // words 0: such an A is not integral for the int32 accumulation)
+    if (af_inexact) m.ai = 0;
     if (ap.active) {
       ap.af = m.af;
       ap.ai = m.ai;
@@ -4426,7 +4447,7 @@ static void pick_value_format(LocalMul& m) {
   uint64_t big_fl = 0;
   for (int b = NSMALL; b < NSMALL + NGCLS; ++b) big_fl += m.sb.flops[b];
   DBuf<PackedRVD>& vd = m.valpd();
-  if (m.af == 0 && bp.nbig > 0 && (vd.p || big_fl >= 4 * (uint64_t)A.nnz)) {
+  if (m.af == 0 && bp.nbig > 0 && (vd.p || big_fl >= (uint64_t)RVD_FLOPS_FACTOR * (uint64_t)A.nnz)) {
     // the f64-valued slab path reads A as (row, f64) records (built once per A,
     // when the big columns' products are enough to pay for its 24 B per entry:
     // GalerkinNew scale 22 packed 68 M entries, 0.34 ms, for 3.7 M products)
@@ -4434,8 +4455,10 @@ static void pick_value_format(LocalMul& m) {
       vd.reset(A.nnz);
       hipLaunchKernelGGL(k_pack_rvd, dim3((unsigned)std::min<int64_t>(nblk(A.nnz, 256), (int64_t)device_cus() * 16)),
                          dim3(256), 0, m.s, A.nnz, A.ir, A.val, vd.p);
+      m.work[CBG_WORK_RVD_BUILT] = 1;
     }
     bp.valAd = vd.p;
+    m.work[CBG_WORK_RVD_USED] = 1;
   }
   bp.iacc = bp.valAp && m.ai == 1 && !m.afh[4] && iacc_bound_ok(m.semiring, m.amax, m.afh[5], m.afh[6]);
   m.work[CBG_WORK_IACC] = bp.iacc ? 1 : 0;

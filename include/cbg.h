@@ -200,9 +200,24 @@ enum {
   CBG_WORK_GRANK0 = 25, /* + k: panel-group rank slabs of <= 2048, 4096 nonzeros */
   CBG_WORK_BIG_CUT = 27, /* the big-column cut in flops (4096, or 1024 where the multiply's rule or
                           * CBG_BIG_FLOPS lowered it): not summed, the call's last multiply's */
-  CBG_WORK_N = 28
+  /* The A-side preparation one MemEfficientSpGEMM / PANEL SUMMA call keeps for its
+   * multiplies (all of the same A): which of them each multiply took from that cache
+   * and which it built.  Each counts multiplies. */
+  CBG_WORK_AMAP_REUSED = 28,  /* reused the cached column map of A */
+  CBG_WORK_PMAP_REUSED = 29,  /* reused the cached panel map */
+  CBG_WORK_PMAP_BUILT = 30,   /* built the full panel map (kept for the call's later multiplies) */
+  CBG_WORK_PMAP_ENTRIES = 31, /* built a private panel map of the A columns their big columns reference */
+  CBG_WORK_AVALS_REUSED = 32, /* had big columns and took A's value verdicts and copies from the cache */
+  CBG_WORK_RVD_BUILT = 33,    /* packed A's (row, f64) records */
+  CBG_WORK_RVD_USED = 34,     /* had slab kernels read the (row, f64) records (packed now or cached) */
+  CBG_WORK_N = 35
 };
 int cbg_last_work_stats(int64_t* counts, int n);
+/* The two thresholds of that preparation: bounds[0] = E, a multiply maps only the A
+ * columns its big columns reference when their B entries x E < A's nonempty columns;
+ * bounds[1] = F, the (row, f64) records are packed by the first multiply whose big
+ * columns carry >= F x nnz(A) flops.  Writes min(n, 2) values, returns 2. */
+int cbg_local_aprep_bounds(int64_t* bounds, int n);
 /* last call's multiway merges (MergeAll / MultiwayMerge): partial entries in,
  * merged entries out, device ms */
 int cbg_merge_stats(int64_t* entries_in, int64_t* entries_out, double* ms);

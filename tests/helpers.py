@@ -729,3 +729,186 @@ def panel_edge_operands(m, sr="plus", nhub=12, hub_rows=3000, nedge=700, seed=9)
     pal = dict(A=[[0.0, -0.0], [0.25, -2.25, 3.0, 1024.125, -1.0], [2.0 ** -140, -3 * 2.0 ** -141], [0.0, -0.0, 1.0]],
                B=_B_PLUS) if sr == "plus" else PALETTES["minplus"]
     return with_palette(Ah, Bh, pal, rng)
+
+
+# --------------------------------------------------------------------------
+# unlike pieces of one phased multiply (tests/test_gpu_aprep_cache.py; the blocks are
+# checked against the thresholds without a device in tests/test_aprep_cases_cpu.py)
+#
+# One MemEfficientSpGEMM / PANEL SUMMA call keeps A's preparation (column map, panel
+# map, f32 / f64 value records, the f32-exact and integral verdicts, max |a|) for all its
+# multiplies; what a piece builds and what it takes over depends on the pieces before
+# it.  A is panel_group_operands()'s A (m = 2^20 + 77: 5 row panels; 4200 stored
+# columns, ~328 k entries) followed by APREP_EMPTY_A empty columns, which give the thin
+# columns their flops-free entries (A's shortest stored column has 8 rows, and a thin
+# column needs fewer than R / 4 = 1.25 products per B entry).  B is P blocks of
+# APREP_W columns, one kind each, so that the phase cuts p * (B.n / P) fall between
+# the blocks and the phase plan's sample (column ids that are multiples of 256) is
+# column 0 of every block.
+# --------------------------------------------------------------------------
+APREP_ENTRIES, APREP_RVD_FLOPS = 64, 4   # cbg.local_aprep_bounds() (tied by test_aprep_bounds_are_the_tested_ones)
+LOW_CUT_FLOPS = 1024                     # csrc/cbg_local.hip LOW_CUT_FLOPS: the cut where the lower-cut rule fires
+GROUP_PRODUCTS = 4096                    # csrc/cbg_local.hip: groups of g panels where flops * g / R <= 4096
+THIN_RATIO = 4                           # csrc/cbg_local.hip THIN_RATIO: thin when flops * 4 < B entries * R (R >= 4)
+APREP_W = 256
+APREP_EMPTY_A = 6000
+_AP_HEAVY, _AP_LIGHT, _AP_LOCAL = 3000, 1000, 200   # panel_group_operands' A columns: 100 rows / 8 rows / 100 rows in panel 0
+APREP_HEAVY_B = float(1 << 20)           # B_heavy's one large value, on A's column 0 (which holds int_big's 2^24)
+APREP_KINDS = ("small", "empty", "lean", "rich", "thin", "B_half", "B_zero", "B_heavy")
+APREP_RICH_LIKE = ("rich", "B_half", "B_zero", "B_heavy")
+APREP_SEQUENCES = {
+    "a": ["small", "lean", "rich", "lean", "empty", "rich", "thin"],
+    "b": ["rich", "lean", "small", "rich"],
+    "c": ["small", "small", "B_half", "rich", "B_zero", "rich", "B_heavy", "rich"],
+    # (c)'s first piece with big columns is B_half, so a B verdict wrongly kept from the
+    # first such piece would be "not integral" for all of (c) and cost no bits; here the
+    # first one is integral and the unlike ones follow
+    "d": ["rich", "B_half", "rich", "B_zero", "B_heavy", "lean"],
+}
+APREP_A_VALUES = {"int": ("plus", "minplus"), "int_big": ("plus", "minplus"), "f32": ("plus",), "f64": ("plus",)}
+_APREP_CACHE = {}
+
+
+def aprep_A(values):
+    """A with one of the four value sets: `int` nonzero integers of magnitude <= 4,
+    `int_big` the same with A's first entry (column 0) = 2^24, `f32` / `f64` the palettes
+    of that name (values by row class: every plus-times sum is exact)"""
+    if "A" not in _APREP_CACHE:
+        Ah = panel_group_operands()[0]
+        Ah = dict(Ah, n=Ah["n"] + APREP_EMPTY_A)
+        assert len(Ah["jc"]) == _AP_HEAVY + _AP_LIGHT + _AP_LOCAL and int(Ah["jc"][-1]) < Ah["n"] - APREP_EMPTY_A
+        _APREP_CACHE["A"] = Ah
+    if ("A", values) not in _APREP_CACHE:
+        Ah = _APREP_CACHE["A"]
+        pal = "int" if values == "int_big" else values
+        dummy = dict(ir=np.zeros(0, np.int32))
+        A = with_palette(Ah, dummy, pal, np.random.default_rng(23))[0]
+        if values == "int_big":
+            A["val"] = A["val"].copy()
+            A["val"][0] = float(1 << 24)
+        _APREP_CACHE[("A", values)] = A
+    return _APREP_CACHE[("A", values)]
+
+
+def _aprep_block(kind, rng):
+    """the columns of one block: a list of (rows of B = columns of A, values), at most
+    APREP_W of them; column 0 is a big column in every kind that has one.  All values are
+    nonzero integers (|v| <= 2, and 1 in the columns of more than 63 entries: every
+    column's sum of |values| stays below 128 = 2^31 / 2^24 outside the thin columns)
+    but for the one entry that names B_half, B_zero and B_heavy."""
+    H0, L0, LOC0, E0 = 0, _AP_HEAVY, _AP_HEAVY + _AP_LIGHT, _AP_HEAVY + _AP_LIGHT + _AP_LOCAL
+
+    def col(lo, n, cnt, mag=2):
+        rows = np.sort(lo + rng.choice(n, int(cnt), replace=False))
+        return rows, (rng.integers(1, mag + 1, len(rows)) * rng.choice([-1, 1], len(rows))).astype(np.float64)
+
+    def heavy(lo, hi, mag=2):
+        return col(H0, _AP_HEAVY, rng.integers(lo, hi + 1), mag)
+
+    def small(n):   # <= 1000 flops: 2..10 heavy columns, or 2..60 light ones (8 rows each)
+        return [heavy(2, 10) if i % 2 else col(L0, _AP_LIGHT, rng.integers(2, 61)) for i in range(n)]
+
+    def mid(n):     # LOW_CUT_FLOPS < flops <= BIG_FLOPS: the columns the lower cut would move
+        return [heavy(12, 38) for _ in range(n)]
+
+    if kind == "empty":
+        return []
+    if kind == "small":
+        return small(200) + mid(20)
+    if kind == "lean":    # one big column of 50 entries; the mid columns outweigh it: the 4096 cut stays
+        return [heavy(50, 50)] + small(60) + mid(6)
+    if kind == "thin":    # an ordinary big column, three thin ones (5500 entries on empty A columns each)
+        cols = [heavy(50, 50)]
+        for nh in (50, 55, 60):
+            r0, v0 = col(E0, APREP_EMPTY_A, 5500)
+            r1, v1 = heavy(nh, nh)
+            cols.append((np.concatenate([r1, r0]), np.concatenate([v1, v0])))
+        return cols + small(30)
+    assert kind in APREP_RICH_LIKE, kind
+    cols = [heavy(58, 58)]
+    special = len(cols)                                    # the first single-panel hash column
+    cols += [heavy(105, 125, mag=1) for _ in range(44)]    # > 2 x 4096 x R / 4 flops: (column, panel) pairs, hash slabs
+    cols += [heavy(42, 51) for _ in range(94)]             # <= 5120 flops: panel groups of 4
+    cols += [heavy(52, 60) for _ in range(71)]             # <= 10240 flops: panel groups of 2
+    cols += [col(LOC0, _AP_LOCAL, rng.integers(45, 61)) for _ in range(10)]           # > 4096 products in panel 0
+    cols += [col(LOC0, _AP_LOCAL, rng.integers(105, 126), mag=1) for _ in range(6)]   # ... as single pairs: bitmap slabs
+    cols += mid(8) + small(20)                             # the lower cut fires: the mid columns run as big ones
+    rows, vals = cols[special]
+    if rows[0] != 0:
+        rows[0] = 0     # A's column 0 (still ascending and distinct)
+    vals[0] = {"rich": vals[0], "B_half": 0.5, "B_zero": 0.0, "B_heavy": APREP_HEAVY_B}[kind]
+    return cols
+
+
+def aprep_B(seq):
+    """(B, kinds) of sequence `seq` (APREP_SEQUENCES): block p holds columns [p * APREP_W, (p + 1) * APREP_W)"""
+    if ("B", seq) not in _APREP_CACHE:
+        kinds = APREP_SEQUENCES[seq]
+        rng = np.random.default_rng(100 + sorted(APREP_SEQUENCES).index(seq))
+        cols, vals = [], []
+        for kind in kinds:
+            blk = _aprep_block(kind, rng)
+            assert len(blk) <= APREP_W
+            cols += [c for c, _ in blk] + [np.zeros(0, np.int64)] * (APREP_W - len(blk))
+            vals += [v for _, v in blk]
+        k = _AP_HEAVY + _AP_LIGHT + _AP_LOCAL + APREP_EMPTY_A
+        Bh = dcsc_from_cols(k, len(cols), cols, np.concatenate(vals))
+        _APREP_CACHE[("B", seq)] = (Bh, list(kinds))
+    return _APREP_CACHE[("B", seq)]
+
+
+def aprep_pieces(Bh, P):
+    """the P column pieces of MemEfficientSpGEMM: cuts at p * (B.n // P), the last to B.n"""
+    w = Bh["n"] // P
+    out, rest = [], Bh
+    for p in range(P - 1):
+        left, rest = split_cols_host(rest, w)
+        out.append(left)
+    return out + [rest]
+
+
+def aprep_refs(seq, values, sr):
+    """the oracle's C of every piece of sequence `seq` (computed once, shared, left unchanged)"""
+    key = ("C", seq, values, sr)
+    if key not in _APREP_CACHE:
+        Bh, kinds = aprep_B(seq)
+        A = aprep_A(values)
+        _APREP_CACHE[key] = [oracle_local(A, Bp, sr) for Bp in aprep_pieces(Bh, len(kinds))]
+    return _APREP_CACHE[key]
+
+
+def aprep_piece_facts(Ah, Bp):
+    """what the multiply's host rules make of one piece, from the oracle's flops per column
+    and the documented thresholds: the big-column cut (BIG_FLOPS, or LOW_CUT_FLOPS where
+    columns in between exist and the columns above BIG_FLOPS carry at least half of the
+    piece's flops; m <= 2^22 holds), the big and thin columns under that cut, their B
+    entries and flops, and B's integrality, largest |value| and largest column sum of |values|"""
+    nz = len(Bp["jc"])
+    if nz == 0:
+        none = np.zeros(0, np.int64)
+        return dict(stored=0, cut=0, nbig=0, nthin=0, big_entries=0, big_flops=0, over_flops=0, flops=0, low_cond=False,
+                    moved=0, col_flops=none, col_big=none.astype(bool), col_thin=none.astype(bool), b_integral=True,
+                    b_max=0.0, b_colsum=0.0, b_zeros=0)
+    f = oracle_symbolic(Ah, Bp)[0].astype(np.int64)
+    ne = np.diff(Bp["cp"]).astype(np.int64)
+    assert (ne >= 2).all()     # (a single-entry column is a scaled copy of A's column whatever its flops)
+    R = (Ah["m"] + PANEL - 1) // PANEL
+    thin_R = R if R >= 4 else 0
+
+    def classes(cut):
+        over = f > cut
+        thin = over & (f * THIN_RATIO < ne * thin_R)
+        return over & ~thin, thin
+
+    big, thin = classes(BIG_FLOPS)
+    moved = (f > LOW_CUT_FLOPS) & (f <= BIG_FLOPS)
+    low_cond = bool(2 * int(f[big | thin].sum()) >= int(f.sum()))
+    cut = LOW_CUT_FLOPS if (moved.any() and low_cond and Ah["m"] <= (1 << 22)) else BIG_FLOPS
+    big, thin = classes(cut)
+    v = np.asarray(Bp["val"], np.float64)
+    colsum = np.add.reduceat(np.abs(v), Bp["cp"][:-1].astype(np.int64))
+    return dict(stored=nz, cut=cut, nbig=int(big.sum()), nthin=int(thin.sum()), big_entries=int(ne[big].sum()),
+                big_flops=int(f[big].sum()), over_flops=int(f[f > BIG_FLOPS].sum()), flops=int(f.sum()),
+                low_cond=low_cond, moved=int(moved.sum()), col_flops=f, col_big=big, col_thin=thin,
+                b_integral=bool((v == np.trunc(v)).all() and (v != 0).all() and (np.abs(v) <= 2.0 ** 24).all()),
+                b_max=float(np.abs(v).max()), b_colsum=float(colsum.max()), b_zeros=int((v == 0).sum()))
