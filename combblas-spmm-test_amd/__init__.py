@@ -522,7 +522,10 @@ WORK_CLASSES = (["bitmap_small_kept", "bitmap_small_mark", "bitmap_large_kept", 
                  "single_big_entries", "hash_bin_columns", "wave_bin_columns", "int_accumulate"] +
                 ["group_rank_N%d" % n for n in (2048, 4096)] + ["big_cut_flops"] +
                 # what each multiply took from / built for the call's cache of A-side preparation
-                ["amap_reused", "pmap_reused", "pmap_built", "pmap_entries", "avals_reused", "rvd_built", "rvd_used"])
+                ["amap_reused", "pmap_reused", "pmap_built", "pmap_entries", "avals_reused", "rvd_built", "rvd_used"] +
+                # the big columns' staged runs (CBG_STAGE_RUNS): multiplies that used them; B entries x panels of
+                # the pairs whose bitmap slabs read them
+                ["staged_multiplies", "staged_entries"])
 
 
 def local_aprep_bounds():

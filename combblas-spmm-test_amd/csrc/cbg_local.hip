@@ -726,7 +726,32 @@ struct SymPanelArgs {
   // per phase at scale 22 / 24), run by panels in k_sym_deferred: (b, col, r0, r1)
   int4* defer;
   int* defer_n;
+  // staged runs (the ST instantiations): every bitmap-mode pair writes each B entry's run of
+  // A(:,k) inside its panel, (start, length), for the numeric's bitmap slabs, which then
+  // read them coalesced instead of hopping through the column-major map in panel-major
+  // order.  Pair (column, panel r), entry j of the column's nb at B position p0 + j:
+  // runs[p0 * R + r * nb + j] -- no offsets to hand out, and a slab finds its pair's runs
+  // from its record's p0, r and nb.
+  int2* runs;
 };
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void st_run(int2* p, int s, int len) {
+  const i32x2 x = {s, len};
+  __builtin_nontemporal_store(x, reinterpret_cast<i32x2*>(p));
+}
+// the runs of pair (column at B positions [p0, p1), panel r): the same for the whole block,
+// so the index is made a scalar (the staging kernels sit at their VGPR cap)
+__device__ __forceinline__ int2* run_base(int2* runs, int64_t p0, int64_t p1, int R, int r) {
+  const int64_t i = p0 * R + (int64_t)r * (p1 - p0);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(i & 0xffffffffu));
+  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)i >> 32));
+  return runs + (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+// (start, end) of a staged run
+__device__ __forceinline__ int2 ld_run(const int2* p) {
+  const i32x2 x = __builtin_nontemporal_load(reinterpret_cast<const i32x2*>(p));
+  return make_int2(x.x, x.x + x.y);
+}
 
 // staging of a unit fetched ahead: ok = 1: p0/p1 of the column; ok = 2: also
 // this thread's first-chunk A run (s, len) over the unit's rows
@@ -805,7 +830,8 @@ __device__ __forceinline__ int hash_claim_drain(int* keys, unsigned mask, const 
 }
 
 // one (column, panel) pair
-template <class H>
+// ST: a bitmap-mode pair writes its staged runs (SymPanelArgs::runs)
+template <bool ST, class H>
 __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLds& L, int b, int col, int r,
                                          const SymPre& pre, H& hook) {
   constexpr int BS = BIG_BS;
@@ -852,12 +878,24 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
     }
     int total;
     const int ex = block_excl_scan<BS>(len, tmp, &total);
+    if constexpr (ST) {
+      // a bitmap-mode pair writes its runs while they are in registers.  The test is the
+      // sparse branch's below, written out a second time on purpose: shared through a
+      // lambda or a device function, both this kernel and k_sym_panel<false, false> spill
+      // (20 / 12 B of scratch at the 64-VGPR cap).  KEEP THE TWO IN STEP: a bitmap-mode
+      // pair without runs would have its slabs gather A at unwritten offsets
+      // (tests/test_gpu_staged_runs.py compares C under both settings bit for bit on pairs
+      // on either side of the test).
+      int Ts = 512;
+      while (Ts * CBG_PAIR_LOAD_DEN < CBG_PAIR_LOAD_NUM * total) Ts <<= 1;
+      if (!(total <= SPARSE_SLAB_MAX && Ts <= pwords) && p < p1) st_run(run_base(a.runs, p0, p1, R, r) + tid, s, len);
+    }
     pref[tid] = ex;
     if (tid == BS - 1) pref[BS] = total;
     st[tid] = seg_stage(s, ex);
     hook(1);
     phase_mark(tmark, 8);
-    int T = 512;
+    int T = 512;  // (the same test as the staged runs' store above)
     while (T * CBG_PAIR_LOAD_DEN < CBG_PAIR_LOAD_NUM * total) T <<= 1;
     if (total <= SPARSE_SLAB_MAX && T <= pwords) {
       // the count of a sparse pair from the panel bitmap: one ds_or per product
@@ -913,6 +951,7 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
       const int2 e = cm(irB[p]);
       s = e.x;
       len = e.y - e.x;
+      if constexpr (ST) st_run(run_base(a.runs, p0, p1, R, r) + (int)(p - p0), s, len);
     }
     int total;
     const int ex = block_excl_scan<BS>(len, tmp, &total);
@@ -1165,7 +1204,8 @@ __device__ __forceinline__ SymPanelLds sym_lds(char* smem, int hwords) {
 }
 // GROUPS: the launch's units span several panels (sym_group); false for the
 // single-panel class, whose kernel then carries no group code (fewer spills)
-template <bool GROUPS>
+// ST (single-panel class only): its bitmap-mode pairs write their staged runs
+template <bool GROUPS, bool ST = false>
 __global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) void k_sym_panel(SymPanelArgs a) {
   // Persistent blocks stride over the units (group-major order kept); the
   // next unit's dependent loads -- column id, B column range, B rows, A run
@@ -1247,7 +1287,7 @@ __global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) voi
       const bool done = r1 > r0 && sym_group(a, L, b, col, r0, r1, cur, hook);
       if (!done && tid == 0) a.defer[atomicAdd(a.defer_n, 1)] = make_int4(b, col, r0, r1);
     } else {
-      sym_pair(a, L, b, col, r0, cur, hook);  // (single-panel units: r1 == r0)
+      sym_pair<ST>(a, L, b, col, r0, cur, hook);  // (single-panel units: r1 == r0)
     }
     hook(3);
     __syncthreads();  // LDS is reused by the next unit
@@ -1257,6 +1297,7 @@ __global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) voi
 }
 
 // the deferred group units, panel by panel (their pairs as in k_sym_panel<false>)
+template <bool ST>
 __global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) void k_sym_deferred(SymPanelArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const SymPanelLds L = sym_lds(smem, a.hwords);
@@ -1266,10 +1307,34 @@ __global__ __launch_bounds__(BIG_BS) __attribute__((amdgpu_waves_per_eu(8))) voi
     const int4 d = a.defer[e];
     const SymPre pp;  // (ok = 0: the pair loads its column range itself)
     for (int r = d.z; r <= d.w; ++r) {
-      sym_pair(a, L, d.x, d.y, r, pp, hook);
+      sym_pair<ST>(a, L, d.x, d.y, r, pp, hook);
       __syncthreads();  // LDS is reused by the next panel
     }
   }
+}
+
+// staged runs the bitmap slabs will read: the B entries of every bitmap-mode pair that got
+// slabs (cbg_last_work_stats; after the symbolic kernels, read back with sync 2)
+__global__ __launch_bounds__(256) void k_runs_staged(int nbig, int R, const int32_t* __restrict__ perm_big,
+                                                     const int64_t* __restrict__ cpB,
+                                                     const int32_t* __restrict__ nslab, const int4* __restrict__ desc,
+                                                     unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long ls;
+  if (threadIdx.x == 0) ls = 0;
+  __syncthreads();
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long n = 0;
+  if (b < nbig) {
+    const int col = perm_big[b];
+    const unsigned long long nb = (unsigned long long)(cpB[col + 1] - cpB[col]);
+    for (int r = 0; r < R; ++r) {
+      const int64_t br = (int64_t)b * R + r;
+      if (nslab[br] > 0 && !(desc[br * NFINE_MAX].w & SLAB_SPARSE)) n += nb;
+    }
+  }
+  if (n) atomicAdd(&ls, n);
+  __syncthreads();
+  if (threadIdx.x == 0 && ls) atomicAdd(out, ls);
 }
 
 // one numeric work item: everything a slab block needs in one 48-byte load
@@ -1996,7 +2061,10 @@ __device__ __forceinline__ void slab_products(int pass, int total, const int* pr
 // marking pass: 397.5-397.9 vs 403.0-404.4 ms at scale 22 (same box)
 // IA: exact int32 accumulation (IACC, see k_int_bound): the value slots hold
 // int32 sums, stored to C as f64
-template <int SR, int CAP, int BS, typename VA, bool KEPT, bool IA>
+// RUNS: every B entry's run of A(:,k) in the slab's panel comes from the symbolic's
+// staged runs (SymPanelArgs::runs, R panels per column), read coalesced next to valB,
+// instead of irB and a hop through the column map pm (neither is then read)
+template <int SR, int CAP, int BS, typename VA, bool KEPT, bool IA, bool RUNS = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_num_slab(const SlabRec* __restrict__ list, int n, int* __restrict__ queue,
                                                  int plog, const int32_t* __restrict__ irB,
                                                  const double* __restrict__ valB, PMap pm,
@@ -2004,7 +2072,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
                                                  const VA* __restrict__ valA,
                                                  int32_t* __restrict__ out_ir,
                                                  double* __restrict__ out_val, const unsigned* __restrict__ gbm,
-                                                 const int* __restrict__ cuts) {
+                                                 const int* __restrict__ cuts, const int2* __restrict__ runs,
+                                                 int R) {
   // Persistent blocks (one per CU at this LDS size) pull slabs from a queue.
   // With one block per CU nothing else hides a slab's dependent global reads,
   // so the next slab's record, kept bitmap words and B staging (irB/valB,
@@ -2050,14 +2119,18 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       }
     }
   };
+  // the runs of the slab's pair: entry j at run_at(rec) + j
+  auto run_at = [&](const SlabRec& r) { return runs + (r.p0 * R + (int64_t)r.r * r.nb); };
   auto fetch_stage1 = [&](const SlabRec& r) {
     if (staged(r) && tid < r.nb) {
-      p_ir = irB[r.p0 + tid];
+      if constexpr (RUNS) p_ce = ld_run(run_at(r) + tid);
+      else p_ir = irB[r.p0 + tid];
       p_bv = valB[r.p0 + tid];
     }
   };
   auto fetch_stage2 = [&](const SlabRec& r) {
-    if (staged(r) && tid < r.nb) p_ce = pm.at(r.r, p_ir);
+    if constexpr (!RUNS)
+      if (staged(r) && tid < r.nb) p_ce = pm.at(r.r, p_ir);
   };
   SlabRec rec = list[i];
   // (thread 0) the dequeue in flight: the slab after the next one -- issued a
@@ -2168,7 +2241,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
           int s = 0, len = 0;
           double bval = 0.0;
           if (p < p1) {
-            const int2 ce = pm.at(rec.r, irB[p]);
+            int2 ce;
+            if constexpr (RUNS) ce = ld_run(run_at(rec) + (p - p0));
+            else ce = pm.at(rec.r, irB[p]);
             if (rec.flags & SLAB_FULL) {
               s = ce.x;
               len = ce.y - ce.x;
@@ -3297,6 +3372,7 @@ struct BigPlan {
   const PackedRV* valAp = nullptr;  // ... and as (row, f32) records
   const PackedRVD* valAd = nullptr;  // A's (row, f64) records when its values are not f32-exact
   DBuf<int> cuts, pcoff;  // multi-slab pairs' cut positions (sym_pair), per-pair offsets
+  DBuf<int2> runs;        // the bitmap-mode pairs' staged runs (SymPanelArgs::runs; null: the map hops)
   const int* gbm_next = nullptr;  // kept-bitmap slots handed out (device), of gbm_slots
   int64_t gbm_slots = 0;
   bool all_kept = false;  // no bitmap-mode pair went without a slot (read with sync 3)
@@ -3325,18 +3401,21 @@ static void launch_slab_bitmap(const SlabRec* list, int n, const BigPlan& bp, co
   if (n <= 0) return;
   auto go = [&](auto k, const auto* valA) {
     launch_queued(k, BS, SlabLds<CAP, BS>::BYTES, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
-                  C.val, bp.gbm.p, bp.cuts.p);
+                  C.val, bp.gbm.p, bp.cuts.p, bp.runs.p, bp.R);
   };
   // (IACC only with the packed records: integers of magnitude <= 2^24 are f32-exact)
-  auto pick = [&](auto kept) {
-    constexpr bool KEPT = decltype(kept)::value;
-    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, true>, bp.valAp);
-    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, false>, bp.valAp);
-    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, KEPT, false>, bp.valAd);
-    else go(k_num_slab<SR, CAP, BS, double, KEPT, false>, A.val);
+  auto pick = [&](auto kept, auto staged) {
+    constexpr bool KEPT = decltype(kept)::value, RUNS = decltype(staged)::value;
+    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, true, RUNS>, bp.valAp);
+    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, false, RUNS>, bp.valAp);
+    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, KEPT, false, RUNS>, bp.valAd);
+    else go(k_num_slab<SR, CAP, BS, double, KEPT, false, RUNS>, A.val);
   };
-  if (bp.all_kept) pick(std::true_type{});
-  else pick(std::false_type{});
+  // (the symbolic wrote the staged runs of every bitmap-mode pair, or none)
+  if (bp.all_kept && bp.runs.p) pick(std::true_type{}, std::true_type{});
+  else if (bp.all_kept) pick(std::true_type{}, std::false_type{});
+  else if (bp.runs.p) pick(std::false_type{}, std::true_type{});
+  else pick(std::false_type{}, std::false_type{});
 }
 
 template <int SR, int NCAP>
@@ -4267,6 +4346,23 @@ static void sym_big_columns(LocalMul& m) {
     CBG_HIP(hipMemsetAsync(bp.pcoff.p, 0xff, sizeof(int) * nbr, s));
     CBG_HIP(hipMemsetAsync(cuts_next.p, 0, sizeof(unsigned long long), s));
   }
+  // Staged runs, all or nothing per multiply: B's entries x R x 8 B (a pair's runs sit at
+  // its column's B position, so the big columns' share of B bounds the waste: taken only
+  // where they hold at least half of B's entries) within min(16 GB, 5 % of the free HBM),
+  // far below what C's planning leaves free (12 B per entry against 60 %).  CBG_STAGE_RUNS=0
+  // (read per call) keeps the map hops; CBG_STAGE_RUNS_CAP (bytes) is a test hook.
+  if (!m.sym_only) {
+    const char* e = getenv("CBG_STAGE_RUNS");
+    const char* ec = getenv("CBG_STAGE_RUNS_CAP");
+    double cap = std::min(16e9, 0.05 * device_bytes_available());
+    if (ec) cap = std::min(cap, atof(ec));
+    const double bytes = (double)B.nnz * bp.R * sizeof(int2);
+    if (!(e && atoi(e) == 0) && 2 * m.big_entries >= B.nnz && bytes <= cap) {
+      bp.runs.reset((size_t)B.nnz * bp.R);
+      m.work[CBG_WORK_STAGED_MULTIPLIES] = 1;
+    }
+  }
+  const bool st = bp.runs.p != nullptr;
   const int pwords = 1 << (bp.plog - 5);
   auto lds_of = [&](int hw) {
     return (size_t)hw * 4 + NFINE_MAX * 4 + (BIG_BS + 4) * 4 + BIG_BS * 4 + (BIG_BS / WAVE + 4) * 4 +
@@ -4274,11 +4370,12 @@ static void sym_big_columns(LocalMul& m) {
   };
   set_lds(k_sym_panel<true>, lds_of(std::max(pwords, GROUP_T)));
   set_lds(k_sym_panel<false>, lds_of(std::max(pwords, GROUP_T)));
+  set_lds(k_sym_panel<false, true>, lds_of(std::max(pwords, GROUP_T)));
   SymPanelArgs sa{bp.perm_big, bp.R, bp.plog, 0, 0, pwords, 0, B.cp, B.ir, bp.pm(), A.ir, A.m,
                   m.cnt.p, bp.cnt_br.p, bp.desc.p, bp.nslab.p, bp.gbm.p, (int)nslots, gbm_next.p,
                   bp.gbm_slot.p,
                   bp.cuts.p, cuts_next.p, cuts_cap,
-                  bp.pcoff.p, nullptr, nullptr};
+                  bp.pcoff.p, nullptr, nullptr, bp.runs.p};
   // group units that overflow one hash slab, collected for k_sym_deferred
   int64_t group_units = 0;
   for (int c = 0; c < NGCLS; ++c)
@@ -4305,24 +4402,41 @@ static void sym_big_columns(LocalMul& m) {
     m.work[sa.glog > 0 ? CBG_WORK_SYM_GROUP_UNITS : CBG_WORK_SYM_PANEL_UNITS] += RG * nc;
     // resident blocks per CU at this launch's LDS size
     const int per_cu = sa.glog > 0 ? blocks_per_cu(k_sym_panel<true>, BIG_BS, lds_of(sa.hwords))
+                       : st        ? blocks_per_cu(k_sym_panel<false, true>, BIG_BS, lds_of(sa.hwords))
                                    : blocks_per_cu(k_sym_panel<false>, BIG_BS, lds_of(sa.hwords));
     // (a multiple of 8: the XCD column order; 8 x ceil(nc / 8) x RG units)
     const int64_t grid = std::min<int64_t>(RG * ((nc + 7) / 8) * 8,
                                            ((int64_t)per_cu * device_cus() * CBG_SYM_WAVES_OF_UNITS) & ~7LL);
     if (sa.glog > 0)
       hipLaunchKernelGGL(k_sym_panel<true>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    else if (st)
+      hipLaunchKernelGGL((k_sym_panel<false, true>), dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
     else
       hipLaunchKernelGGL(k_sym_panel<false>, dim3((unsigned)grid), dim3(BIG_BS), lds_of(sa.hwords), s, sa);
   }
   if (group_units > 0) {
     sa.hwords = std::max(pwords, GROUP_T);
-    set_lds(k_sym_deferred, lds_of(sa.hwords));
-    hipLaunchKernelGGL(k_sym_deferred, dim3((unsigned)std::min<int64_t>(group_units, device_cus() * 4)),
-                       dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    const dim3 gd((unsigned)std::min<int64_t>(group_units, device_cus() * 4));
+    if (st) {
+      set_lds(k_sym_deferred<true>, lds_of(sa.hwords));
+      hipLaunchKernelGGL(k_sym_deferred<true>, gd, dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    } else {
+      set_lds(k_sym_deferred<false>, lds_of(sa.hwords));
+      hipLaunchKernelGGL(k_sym_deferred<false>, gd, dim3(BIG_BS), lds_of(sa.hwords), s, sa);
+    }
     CBG_HIP(hipMemcpyAsync(reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS)) + 5, defer_n.p, sizeof(int),
                            hipMemcpyDeviceToHost, s));
     df.take(defer);
     df.take(defer_n);
+  }
+  if (st) {
+    DBuf<unsigned long long> nst(1);
+    CBG_HIP(hipMemsetAsync(nst.p, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_runs_staged, dim3(nblk(nbig, 256)), dim3(256), 0, s, nbig, bp.R, bp.perm_big, B.cp,
+                       bp.nslab.p, bp.desc.p, nst.p);
+    CBG_HIP(hipMemcpyAsync(reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS)) + 6, nst.p, sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    df.take(nst);
   }
   // the symbolic kernels may still run: the counters stay allocated until the
   // multiply's last synchronization
@@ -4414,6 +4528,7 @@ static void scan_counts(LocalMul& m) {
   m.flops_total = scal[3];
   m.single_big_entries = scal[4];
   m.work[CBG_WORK_SYM_DEFERRED_UNITS] = scal[5];
+  m.work[CBG_WORK_STAGED_ENTRIES] = scal[6];
   for (int b = 1; b <= SYM_FUSED_LAST; ++b) m.work[CBG_WORK_ESC_COLUMNS] += m.sb.count[b];
   m.work[CBG_WORK_THIN_COLUMNS] = m.thin_R ? m.sb.count[THIN_BIN] : 0;
   m.work[CBG_WORK_SINGLE_BIG_ENTRIES] = m.single_big_entries;
@@ -4653,6 +4768,7 @@ void local_spgemm_impl(const cbg_tile& A, const cbg_tile& B, int semiring, cbg_t
   LocalMul m(A, B, semiring, C, s, sink, sym_only);
   CBG_HIP(hipEventRecord(m.ts.ev0, s));
   reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS))[5] = 0;  // deferred group units (sync 2)
+  reinterpret_cast<int64_t*>(host_stage(STAGE_SCALARS))[6] = 0;  // staged runs written (sync 2)
   prep_a_maps(m);
   plan_symbolic_bins(m);  // sync 1
   sym_small_columns(m);

@@ -210,7 +210,13 @@ enum {
   CBG_WORK_AVALS_REUSED = 32, /* had big columns and took A's value verdicts and copies from the cache */
   CBG_WORK_RVD_BUILT = 33,    /* packed A's (row, f64) records */
   CBG_WORK_RVD_USED = 34,     /* had slab kernels read the (row, f64) records (packed now or cached) */
-  CBG_WORK_N = 35
+  /* Staged runs: the big columns' symbolic writes every B entry's run of A(:,k) inside each
+   * panel of its bitmap-mode (column, panel) pairs, and the numeric's bitmap slabs read them
+   * instead of hopping through A's panel map (all or nothing per multiply; CBG_STAGE_RUNS=0
+   * keeps the hops). */
+  CBG_WORK_STAGED_MULTIPLIES = 35, /* multiplies that used staged runs */
+  CBG_WORK_STAGED_ENTRIES = 36,    /* B entries x panels of the pairs whose bitmap slabs read them */
+  CBG_WORK_N = 37
 };
 int cbg_last_work_stats(int64_t* counts, int n);
 /* The two thresholds of that preparation: bounds[0] = E, a multiply maps only the A
