@@ -40,7 +40,7 @@ RANDOM_VALUES_SEED = 0x5EEDF00D  # Tile.set_random_values default
 PHASES_AUTO = -1  # MemEfficientSpGEMM: phase count from the device's free memory (include/cbg.h CBG_PHASES_AUTO)
 
 GRIDMISMATCH, DIMMISMATCH, NOTSQUARE, MATRIXALIAS, INVALIDPARAMS = 3001, 3002, 3003, 3005, 3007
-HIPERROR, RCCLERROR, OOM, NOTSUPPORTED = 3100, 3101, 3102, 3103
+HIPERROR, RCCLERROR, OOM, NOTSUPPORTED, INTERNAL = 3100, 3101, 3102, 3103, 3104
 
 
 class CbgError(RuntimeError):
@@ -82,7 +82,7 @@ EXPORTS = [
     "cbg_grid_transpose", "cbg_grid_block_extract", "cbg_grid_agree", "cbg_merge_stats", "cbg_tile_alloc",
     "cbg_tile_concat_cols", "cbg_device_memory", "cbg_last_summa_info", "cbg_summa_spgemm_memeff",
     "cbg_last_summa_comm",
-    "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_local_aprep_bounds", "cbg_store_probe",
+    "cbg_last_phase_plan", "cbg_last_work_stats", "cbg_local_aprep_bounds", "cbg_local_slab_caps", "cbg_store_probe",
     "cbg_tile_col_stats", "cbg_tile_prune_column", "cbg_grid_kselect", "cbg_grid_mcl_prune", "cbg_summa_spgemm_mcl",
     "cbg_mcl_kselect_bounds", "cbg_last_mcl_stats",
     "cbg_grid_reduce_cols", "cbg_mcl_moment_bounds", "cbg_tile_apply", "cbg_grid_make_col_stochastic", "cbg_grid_chaos",
@@ -194,6 +194,7 @@ def lib():
                                   ctypes.POINTER(CMclParams)], i32),
         "cbg_mcl_kselect_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_local_aprep_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_local_slab_caps": ([ctypes.POINTER(i32)], i32),
         "cbg_last_mcl_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_grid_reduce_cols": ([vp, T, i32, ctypes.c_double, vp], i32),
         "cbg_mcl_moment_bounds": ([ctypes.POINTER(i64), i32], i32),
@@ -525,7 +526,9 @@ WORK_CLASSES = (["bitmap_small_kept", "bitmap_small_mark", "bitmap_large_kept", 
                 ["amap_reused", "pmap_reused", "pmap_built", "pmap_entries", "avals_reused", "rvd_built", "rvd_used"] +
                 # the big columns' staged runs (CBG_STAGE_RUNS): multiplies that used them; B entries x panels of
                 # the pairs whose bitmap slabs read them
-                ["staged_multiplies", "staged_entries"])
+                ["staged_multiplies", "staged_entries"] +
+                # the check on the symbolic's slab plan: bitmap slabs beyond their launch class's cap (always 0)
+                ["slab_over_cap"])
 
 
 def local_aprep_bounds():
@@ -534,6 +537,15 @@ def local_aprep_bounds():
     b = (ctypes.c_int64 * 2)()
     n = lib().cbg_local_aprep_bounds(b, 2)
     return [int(x) for x in b[:n]]
+
+
+def local_slab_caps():
+    """the bitmap slab classes' caps in nonzeros: [small, large] where the slabs sum
+    f64 values, then [small, large] where they sum exact integers in int32
+    (cbg_local_slab_caps)"""
+    c = (ctypes.c_int32 * 4)()
+    lib().cbg_local_slab_caps(c)
+    return [int(x) for x in c]
 
 
 def last_work_stats():

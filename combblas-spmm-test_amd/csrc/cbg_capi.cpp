@@ -413,6 +413,7 @@ int cbg_last_work_stats(int64_t* counts, int n) {
 }
 
 int cbg_local_aprep_bounds(int64_t* bounds, int n) { return cbg::local_aprep_bounds(bounds, n); }
+int cbg_local_slab_caps(int out[4]) { return cbg::local_slab_caps(out); }
 
 // ---------------- grid ----------------
 int cbg_get_unique_id(void* id);  // cbg_summa_id.cpp

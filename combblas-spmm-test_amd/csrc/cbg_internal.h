@@ -261,6 +261,8 @@ struct APrepScope {
 // the preparation's thresholds (cbg_local_aprep_bounds): the entries factor of the
 // private panel map and the flops factor of the (row, f64) records
 int local_aprep_bounds(int64_t* bounds, int n);
+// the bitmap slab classes' caps (cbg_local_slab_caps): small, large for f64 sums, then for int32 sums
+int local_slab_caps(int out[4]);
 
 // device exclusive scan of n int64 values -> out[0..n], returns nothing (total at out[n]).
 // df: the scan's temporaries are released with df (no host synchronization);

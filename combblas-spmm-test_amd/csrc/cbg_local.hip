@@ -578,6 +578,51 @@ constexpr int PANEL_LOG_MAX = CBG_PANEL_LOG_MAX;  // max rows of a panel (LDS bi
 static_assert(SLAB_CAP >= (1 << FINE_LOG), "a fine range must fit one slab");
 constexpr int SLAB_WORDS = 1 << (PANEL_LOG_MAX - 5);
 constexpr int NFINE_MAX = 1 << (PANEL_LOG_MAX - FINE_LOG);  // fine ranges (= max slabs) per panel
+// LDS of a bitmap slab (k_num_slab) and the caps of its two launch classes: small
+// slabs run 2 workgroups of 512 per CU, large ones get the CU's whole LDS.
+// IA: the value region holds int32 sums and, behind them, the low 16 bits of
+// each nonzero's row above the slab's `lo` at its rank (6 B per nonzero, not 8):
+// a slab spans at most one panel of 2^18 rows and its rows leave LDS in rank
+// order, so the top two bits are a step function of the rank whose steps the
+// rank scan's wpre already holds (k_num_slab's output loop)
+template <int CAP, int BS, bool IA = false>
+struct SlabLds {
+  // vals[CAP] f64 (IA: sums[CAP] i32 | rows[CAP] u16) | bv[BS] f64 | bm[SLAB_WORDS] | pref[BS+4] | st[BS] |
+  // tmp[BS/64+4] | (pad 16) wpre[SLAB_WORDS] u16
+  static constexpr int VAL_BYTES = CAP * (IA ? 6 : 8);
+  static constexpr int FIXED = BS * 8 + SLAB_WORDS * 4 + (BS + 4) * 4 + BS * 4 + (BS / WAVE + 4) * 4;
+  static constexpr int WPRE_OFF = (VAL_BYTES + FIXED + 15) & ~15;
+  static constexpr int BYTES = WPRE_OFF + SLAB_WORDS * 2;
+  static_assert(CAP % 8 == 0 && BYTES <= 160 * 1024, "slab LDS");
+  // the largest CAP (a multiple of 8) of a layout of at most `bytes` bytes
+  static constexpr int cap_for(int bytes) {
+    return (bytes - SLAB_WORDS * 2 - ((FIXED + 15) & ~15)) / (IA ? 6 : 8) & ~7;
+  }
+};
+constexpr int SLAB_LDS_CU = 160 * 1024;
+#ifndef CBG_SLAB_SMALL_CAP  // the largest value array that keeps 2 blocks of 512 per CU (81856 B of LDS):
+#define CBG_SLAB_SMALL_CAP 3056  // 412.6-414.4 vs 418.2-419.4 ms at 2048 (scale 22, same box)
+#endif
+constexpr int SLAB_SMALL_CAP = CBG_SLAB_SMALL_CAP, SLAB_SMALL_BS = 512;
+constexpr int SLAB_LARGE_CAP = SLAB_CAP, SLAB_LARGE_BS = CBG_SLAB_LARGE_BS;
+// ... and under IACC, at 6 B per nonzero: 4080 (81888 B)
+#ifndef CBG_SLAB_SMALL_CAP_IA
+#define CBG_SLAB_SMALL_CAP_IA (SlabLds<8, SLAB_SMALL_BS, true>::cap_for(SLAB_LDS_CU / 2))
+#endif
+constexpr int SLAB_SMALL_CAP_IA = CBG_SLAB_SMALL_CAP_IA;
+static_assert(SLAB_SMALL_CAP_IA >= SLAB_SMALL_CAP && SLAB_SMALL_CAP_IA <= SLAB_LARGE_CAP &&
+                  2 * SlabLds<SLAB_SMALL_CAP_IA, SLAB_SMALL_BS, true>::BYTES <= SLAB_LDS_CU,
+              "two small IACC slabs per CU");
+// the large class under IACC: one block of 1024 with the whole LDS, 16368 (163840 B).  The
+// symbolic plans a pair's slabs against this cap where the multiply's IACC verdict is
+// known on the device (SymPanelArgs::iacc_dev), against SLAB_CAP otherwise
+#ifndef CBG_SLAB_LARGE_CAP_IA
+#define CBG_SLAB_LARGE_CAP_IA (SlabLds<8, SLAB_LARGE_BS, true>::cap_for(SLAB_LDS_CU))
+#endif
+constexpr int SLAB_LARGE_CAP_IA = CBG_SLAB_LARGE_CAP_IA;
+static_assert(SLAB_LARGE_CAP_IA >= SLAB_LARGE_CAP && SLAB_LARGE_CAP_IA < 65536 &&
+                  SlabLds<SLAB_LARGE_CAP_IA, SLAB_LARGE_BS, true>::BYTES <= SLAB_LDS_CU,
+              "one large IACC slab per CU, ranks of 16 bits");
 #ifndef CBG_BIG_BS
 #define CBG_BIG_BS 512
 #endif
@@ -733,6 +778,9 @@ struct SymPanelArgs {
   // runs[p0 * R + r * nb + j] -- no offsets to hand out, and a slab finds its pair's runs
   // from its record's p0, r and nb.
   int2* runs;
+  // the multiply's IACC verdict (k_iacc_verdict; null: none, the symbolic alone): its
+  // bitmap slabs hold up to SLAB_LARGE_CAP_IA nonzeros
+  const int* iacc_dev;
 };
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void st_run(int2* p, int s, int len) {
@@ -1014,16 +1062,18 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
   phase_mark(tmark, 11);
   if (tid < WAVE) {
     // slab plan by wave 0 (nfine <= 64): one slab from the first to the last
-    // non-empty fine range when the pair fits SLAB_CAP, else lane 0 groups
-    // consecutive fine ranges greedily while a slab holds <= SLAB_CAP
+    // non-empty fine range when the pair fits the slab cap, else lane 0 groups
+    // consecutive fine ranges greedily while a slab holds <= the cap
     static_assert(NFINE_MAX <= WAVE, "fine ranges per panel");
     const int cf = tid < nfine ? fine[tid] : 0;
     const int total = wave_sum(cf);
+    // (uniform: the verdict's word is read once per pair into a scalar)
+    const int cap = (a.iacc_dev && __builtin_amdgcn_readfirstlane(*a.iacc_dev)) ? SLAB_LARGE_CAP_IA : SLAB_CAP;
     const unsigned long long nzmask = __ballot(cf != 0);
     int4* d = desc + (int64_t)br * NFINE_MAX;
     if (tid == 0) {
       int ns = 0;
-      if (total > 0 && total <= SLAB_CAP) {
+      if (total > 0 && total <= cap) {
         const int f0 = __ffsll((long long)nzmask) - 1;
         const int f1 = 63 - __clzll((long long)nzmask);
         d[0] = make_int4(R0 + (f0 << FINE_LOG), min(R0 + ((f1 + 1) << FINE_LOG), R1), 0, total);
@@ -1035,7 +1085,7 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
           if (c == 0) continue;
           const int lo = R0 + (f << FINE_LOG);
           const int hi = min(lo + (1 << FINE_LOG), R1);
-          if (g_cnt && g_cnt + c > SLAB_CAP) {
+          if (g_cnt && g_cnt + c > cap) {
             d[ns++] = make_int4(g_lo, g_hi, run - g_cnt, g_cnt);
             g_cnt = 0;
           }
@@ -1400,10 +1450,11 @@ __device__ __forceinline__ int slab_class(const int4& d, int small_cap, int rank
 constexpr int SLAB_KEYS_MAX = 8192;
 __host__ __device__ inline int slab_kr(int R) { return SLAB_NCLS * R <= SLAB_KEYS_MAX ? R : 1; }
 
-// pass 1: within-panel -> within-column offsets, (class, panel) counts
+// pass 1: within-panel -> within-column offsets, (class, panel) counts; *over:
+// the bitmap slabs of more than large_cap nonzeros (the host's check, plan_slabs)
 __global__ void k_slab_count(int nbig, int R, const int32_t* __restrict__ nslab, const int32_t* __restrict__ cnt_br,
-                             int4* __restrict__ desc, int small_cap, int rank_span, int rank_min,
-                             int grank_min, int* __restrict__ counts) {
+                             int4* __restrict__ desc, int small_cap, int large_cap, int rank_span, int rank_min,
+                             int grank_min, int* __restrict__ counts, int* __restrict__ over) {
   extern __shared__ int lc[];  // [SLAB_NCLS * KR]
   const int KR = slab_kr(R), NK = SLAB_NCLS * KR;
   for (int k = threadIdx.x; k < NK; k += blockDim.x) lc[k] = 0;
@@ -1416,6 +1467,8 @@ __global__ void k_slab_count(int nbig, int R, const int32_t* __restrict__ nslab,
       for (int s = 0; s < nslab[br]; ++s) {
         int4& d = desc[(int64_t)br * NFINE_MAX + s];
         d.z += off;
+        // (a bitmap slab planned beyond the cap of the large class about to be launched)
+        if (!(d.w & SLAB_SPARSE) && d.w > large_cap) atomicAdd(over, 1);
         atomicAdd(&lc[slab_class(d, small_cap, rank_span, rank_min, grank_min) * KR + (KR > 1 ? r : 0)], 1);
       }
       off += cnt_br[br];
@@ -1988,20 +2041,6 @@ __device__ __forceinline__ void st_rows(T* p, T v) {
   if constexpr (IA) st_emit(p, v);
   else *p = v;
 }
-template <int CAP, int BS>
-struct SlabLds {
-  // vals[CAP] f64 | bv[BS] f64 | bm[SLAB_WORDS] | pref[BS+4] | st[BS] | tmp[BS/64+4] | (pad 16) wpre[SLAB_WORDS] u16
-  static constexpr int WPRE_OFF =
-      ((CAP * 8 + BS * 8 + SLAB_WORDS * 4 + (BS + 4) * 4 + BS * 4 + (BS / WAVE + 4) * 4) + 15) & ~15;
-  static constexpr int BYTES = WPRE_OFF + SLAB_WORDS * 2;
-  static_assert(BYTES <= 160 * 1024, "slab LDS");
-};
-#ifndef CBG_SLAB_SMALL_CAP  // the largest value array that keeps 2 blocks of 512 per CU (81856 B of LDS):
-#define CBG_SLAB_SMALL_CAP 3056  // 412.6-414.4 vs 418.2-419.4 ms at 2048 (scale 22, same box)
-#endif
-constexpr int SLAB_SMALL_CAP = CBG_SLAB_SMALL_CAP, SLAB_SMALL_BS = 512;
-constexpr int SLAB_LARGE_CAP = SLAB_CAP, SLAB_LARGE_BS = CBG_SLAB_LARGE_BS;
-
 // A's (row, value) of product position q
 // (VA = float: A's values narrowed losslessly, see k_vals_f32; the widening is
 // exact; VA = PackedRV: the same as (row, f32) records, one gather per product)
@@ -2023,14 +2062,14 @@ struct RankVal {
   int rank, row;
   double v;
 };
-// IA: int32 sums in vals' first CAP ints, and each product's row written at its
-// rank into rows[] (the value region's second half; duplicates write the same
-// row), so the output copies the rows instead of walking the bitmap
+// IA: int32 sums in vals' first CAP ints, and the low 16 bits of each product's
+// row above lo written at its rank into rows[] (behind the sums; duplicates
+// write the same row), so the output copies the rows instead of walking the bitmap
 template <int SR, int BS, typename VA, bool IA>
 __device__ __forceinline__ void slab_products(int pass, int total, const int* pref, const int* st, const double* bv,
                                               const int32_t* __restrict__ irA, const VA* __restrict__ valA,
                                               int lo, unsigned* bm, const unsigned short* wpre, double* vals,
-                                              int* rows) {
+                                              unsigned short* rows) {
   if (pass == 0) {
     block_products<BS>(
         pref, total, [&](int sg) { return SegI{seg_off(st, pref, sg)}; },
@@ -2048,7 +2087,7 @@ __device__ __forceinline__ void slab_products(int pass, int total, const int* pr
         [&](const RankVal& x) {
           if constexpr (IA) {
             SemI<SR>::lds_acc(reinterpret_cast<int*>(vals) + x.rank, x.v);
-            rows[x.rank] = lo + x.row;
+            rows[x.rank] = (unsigned short)x.row;
           } else {
             Sem<SR>::lds_acc(&vals[x.rank], x.v);
           }
@@ -2081,16 +2120,16 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
   // slab runs its rank scan, products and output.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* vals = reinterpret_cast<double*>(smem);                          // [CAP]
-  double* bv = vals + CAP;                                                 // [BS]
+  double* bv = reinterpret_cast<double*>(smem + SlabLds<CAP, BS, IA>::VAL_BYTES);  // [BS]
   unsigned* bm = reinterpret_cast<unsigned*>(bv + BS);                     // [SLAB_WORDS]
   int* pref = reinterpret_cast<int*>(bm + SLAB_WORDS);                     // [BS+1]
   int* st = pref + BS + 4;                                                 // [BS]
   int* tmp = st + BS;                                                      // scan scratch + queue slot
   // [SLAB_WORDS], 16-B aligned; a constant offset from smem keeps the LDS
   // address space (a uintptr_t round-up would turn its reads into flat loads)
-  unsigned short* wpre = reinterpret_cast<unsigned short*>(smem + SlabLds<CAP, BS>::WPRE_OFF);
+  unsigned short* wpre = reinterpret_cast<unsigned short*>(smem + SlabLds<CAP, BS, IA>::WPRE_OFF);
   constexpr int WPT = SLAB_WORDS / BS;
-  static_assert(WPT % 8 == 0 && (CAP * 8 + BS * 8) % 16 == 0, "rank scan vectors");
+  static_assert(WPT % 8 == 0 && (SlabLds<CAP, BS, IA>::VAL_BYTES + BS * 8) % 16 == 0, "rank scan vectors");
   const int tid = threadIdx.x;
   const int wslot = 1 << (plog - 5);
   constexpr int NW = BS / WAVE;
@@ -2279,7 +2318,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         if ((c_dbg & 32) && pass == 1 && tid == 0) atomicAdd(&g_stat[4], (unsigned long long)total);
         if (!(c_dbg & (2 << pass)))
           slab_products<SR, BS, VA, IA>(pass, total, pref, st, bv, irA, valA, lo, bm, wpre, vals,
-                                        reinterpret_cast<int*>(vals) + CAP);
+                                        reinterpret_cast<unsigned short*>(reinterpret_cast<int*>(vals) + CAP));
         __syncthreads();
         phase_mark(tmark, 4 + pass);
       }
@@ -2287,9 +2326,18 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
     if (has_next) fetch_stage2(nrec);
     if (IA && !(c_dbg & 8)) {
       // rows and values in rank order (C's order): coalesced copies
+      // (row = lo + (k << 16 | rows[j]), k the number of the 2^16-row ranges'
+      // first ranks t1 <= t2 <= t3 that are <= j: the rank scan wrote every
+      // word's prefix, nout past the slab's last word)
       const int* ivals = reinterpret_cast<const int*>(vals);
+      const unsigned short* rows = reinterpret_cast<const unsigned short*>(ivals + CAP);
+      constexpr int W16 = 65536 / 32;
+      static_assert(SLAB_WORDS <= 4 * W16, "a slab's rows above lo take 18 bits");
+      const int t1 = W16 < SLAB_WORDS ? wpre[W16] : nout, t2 = 2 * W16 < SLAB_WORDS ? wpre[2 * W16] : nout,
+                t3 = 3 * W16 < SLAB_WORDS ? wpre[3 * W16] : nout;
       for (int j = tid; j < nout; j += BS) {
-        st_rows<true>(&out_ir[obase + j], ivals[CAP + j]);
+        const int k = (j >= t1) + (j >= t2) + (j >= t3);
+        st_rows<true>(&out_ir[obase + j], lo + ((k << 16) | rows[j]));
         st_stream(&out_val[obase + j], (double)ivals[j]);
       }
     } else if (!(c_dbg & 8)) {
@@ -3395,18 +3443,25 @@ static void launch_slab_hash(const SlabRec* list, int n, const BigPlan& bp, cons
   else go(k_num_slab_hash<SR, T, BS, false, double>, A.val);
 }
 
-template <int SR, int CAP, int BS>
+// CAP_IA: the class's cap under IACC (6 B of LDS per nonzero, SlabLds); PER_CU:
+// the blocks per CU the class's caps were derived for
+template <int SR, int CAP, int CAP_IA, int BS, int PER_CU>
 static void launch_slab_bitmap(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                                const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  auto go = [&](auto k, const auto* valA) {
-    launch_queued(k, BS, SlabLds<CAP, BS>::BYTES, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
-                  C.val, bp.gbm.p, bp.cuts.p, bp.runs.p, bp.R);
+  auto go_lds = [&](auto k, size_t lds, const auto* valA) {
+    set_lds(k, lds);
+    if (blocks_per_cu(k, BS, lds) < PER_CU)
+      throw HipError("bitmap slab class: fewer resident blocks per CU than its cap was derived for", CBG_ERR_INTERNAL);
+    launch_queued(k, BS, lds, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val, bp.gbm.p,
+                  bp.cuts.p, bp.runs.p, bp.R);
   };
+  auto go = [&](auto k, const auto* valA) { go_lds(k, SlabLds<CAP, BS>::BYTES, valA); };
   // (IACC only with the packed records: integers of magnitude <= 2^24 are f32-exact)
   auto pick = [&](auto kept, auto staged) {
     constexpr bool KEPT = decltype(kept)::value, RUNS = decltype(staged)::value;
-    if (bp.iacc) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, true, RUNS>, bp.valAp);
+    if (bp.iacc)
+      go_lds(k_num_slab<SR, CAP_IA, BS, PackedRV, KEPT, true, RUNS>, SlabLds<CAP_IA, BS, true>::BYTES, bp.valAp);
     else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, false, RUNS>, bp.valAp);
     else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, KEPT, false, RUNS>, bp.valAd);
     else go(k_num_slab<SR, CAP, BS, double, KEPT, false, RUNS>, A.val);
@@ -3465,8 +3520,8 @@ static void launch_slabs(const SlabRec* list, const int* ncls, const BigPlan& bp
   }
   // (hash classes queued behind the small-column bins on the side stream were
   // 3-4 % slower at scale 22: every slab class runs on the main stream)
-  launch_slab_bitmap<SR, SLAB_SMALL_CAP, SLAB_SMALL_BS>(at[0], ncls[0], bp, A, B, C, s, df);
-  launch_slab_bitmap<SR, SLAB_LARGE_CAP, SLAB_LARGE_BS>(at[1], ncls[1], bp, A, B, C, s, df);
+  launch_slab_bitmap<SR, SLAB_SMALL_CAP, SLAB_SMALL_CAP_IA, SLAB_SMALL_BS, 2>(at[0], ncls[0], bp, A, B, C, s, df);
+  launch_slab_bitmap<SR, SLAB_LARGE_CAP, SLAB_LARGE_CAP_IA, SLAB_LARGE_BS, 1>(at[1], ncls[1], bp, A, B, C, s, df);
   static_assert(SLAB_HASH_NCLS == 9, "hash slab classes (CBG_HASH_TABLES)");
   launch_slab_hash<SR, 512, 256>(at[2], ncls[2], bp, A, B, C, s, df);
   launch_slab_hash<SR, 768, 256>(at[3], ncls[3], bp, A, B, C, s, df);
@@ -3813,9 +3868,31 @@ __global__ __launch_bounds__(256) void k_col_int_bound(int64_t nzc, const int64_
   }
   block_int_bound_out(bad, mx, cs, out);
 }
-static bool iacc_bound_ok(int semiring, int amax, int bmax, int bcolsum) {
-  if (semiring == CBG_MIN_PLUS) return (int64_t)amax + bmax < (1LL << 30);
+__host__ __device__ inline bool iacc_bound_ok(int semiring, int amax, int bmax, int bcolsum) {
+  if (semiring == CBG_MIN_PLUS) return (long long)amax + bmax < (1LL << 30);
   return (double)amax * (double)bcolsum < 2147483648.0;
+}
+// The IACC rule, for the host and the device: A read as (row, f32) records (packed:
+// requested and A f32-exact), A and B integral, and the sums bounded.
+__host__ __device__ inline bool iacc_rule(int semiring, bool packed, bool a_integral, int amax, bool b_integral,
+                                          int bmax, int bcolsum) {
+  return packed && a_integral && b_integral && iacc_bound_ok(semiring, amax, bmax, bcolsum);
+}
+// The multiply's verdict on the device, before its symbolic plans the big columns'
+// slabs: aflag = k_vals_f32's and k_int_bound's words ([0] A not f32-exact, [1] not
+// integral, [2] max |a|), or null with A's verdicts from the call's cache (af, ai,
+// amax); bint = k_col_int_bound's words, or null where B was not checked.
+__global__ void k_iacc_verdict(const int* __restrict__ aflag, const int* __restrict__ bint, int semiring, int packed,
+                               int af, int ai, int amax, int* __restrict__ iacc_dev) {
+  if (aflag) {
+    af = aflag[0] ? 0 : 1;
+    ai = (aflag[0] || aflag[1]) ? 0 : 1;
+    amax = aflag[2];
+  }
+  const bool b_int = bint && !bint[0];
+  const bool on =
+      iacc_rule(semiring, packed && af == 1, ai == 1, amax, b_int, b_int ? bint[1] : 0, b_int ? bint[2] : 0);
+  *iacc_dev = on ? 1 : 0;
 }
 
 // A's (row, f64) records for the f64-valued slab path
@@ -3865,6 +3942,11 @@ int local_aprep_bounds(int64_t* bounds, int n) {
   const int64_t b[2] = {PMAP_ENTRIES_FACTOR, RVD_FLOPS_FACTOR};
   for (int i = 0; bounds && i < n && i < 2; ++i) bounds[i] = b[i];
   return 2;
+}
+int local_slab_caps(int out[4]) {
+  const int c[4] = {SLAB_SMALL_CAP, SLAB_LARGE_CAP, SLAB_SMALL_CAP_IA, SLAB_LARGE_CAP_IA};
+  for (int i = 0; out && i < 4; ++i) out[i] = c[i];
+  return 0;
 }
 void aprep_begin() { aprep().active = true; }
 void aprep_end() {
@@ -4009,9 +4091,10 @@ struct LocalMul {
   DBuf<PackedRVD>& valpd() { return ap.active ? ap.valpd : valpd_own; }
   // A's verdicts (cached with the maps): f32-exact, integral, max |a|
   int af = -1, ai = -1, amax = 0;
-  DBuf<int> af_flag, bint;
+  DBuf<int> af_flag, bint, iacc_dev;
   // [0] A not f32-exact | [1] A not integral, [2] max |a| | [4] B not integral,
-  // [5] max |b|, [6] B's largest column |sum| (IACC; read with sync 2)
+  // [5] max |b|, [6] B's largest column |sum| | [7] the IACC verdict (k_iacc_verdict;
+  // read with sync 2)
   int* afh = nullptr;
   // after the symbolic: C's column pointers, the slab lists, the numeric's bins
   DBuf<int64_t> colptr, sbase;
@@ -4250,6 +4333,14 @@ static void check_values(LocalMul& m) {
                        0, s, B.nzc, B.cp, B.val, m.bint.p, m.af_flag.p);
     CBG_HIP(hipMemcpyAsync(m.afh + 4, m.bint.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
   }
+  // the verdict, on the device for the symbolic's slab plan and for the host with sync 2
+  m.afh[7] = 0;
+  if (nbig > 0 && !m.sym_only) {
+    m.iacc_dev.reset(1);
+    hipLaunchKernelGGL(k_iacc_verdict, dim3(1), dim3(1), 0, s, m.af_flag.p, m.bint.p, m.semiring,
+                       m.valp().p ? 1 : 0, m.af, m.ai, m.amax, m.iacc_dev.p);
+    CBG_HIP(hipMemcpyAsync(m.afh + 7, m.iacc_dev.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  }
 }
 
 // panel column maps of A (reused across phases like cmap)
@@ -4375,7 +4466,7 @@ static void sym_big_columns(LocalMul& m) {
                   m.cnt.p, bp.cnt_br.p, bp.desc.p, bp.nslab.p, bp.gbm.p, (int)nslots, gbm_next.p,
                   bp.gbm_slot.p,
                   bp.cuts.p, cuts_next.p, cuts_cap,
-                  bp.pcoff.p, nullptr, nullptr, bp.runs.p};
+                  bp.pcoff.p, nullptr, nullptr, bp.runs.p, m.iacc_dev.p};
   // group units that overflow one hash slab, collected for k_sym_deferred
   int64_t group_units = 0;
   for (int c = 0; c < NGCLS; ++c)
@@ -4575,7 +4666,8 @@ static void pick_value_format(LocalMul& m) {
     bp.valAd = vd.p;
     m.work[CBG_WORK_RVD_USED] = 1;
   }
-  bp.iacc = bp.valAp && m.ai == 1 && !m.afh[4] && iacc_bound_ok(m.semiring, m.amax, m.afh[5], m.afh[6]);
+  bp.iacc = m.afh[7] != 0;  // (decided once, on the device: the symbolic planned its slabs by it)
+  if (bp.iacc && !bp.valAp) throw HipError("IACC verdict without A's (row, f32) records", CBG_ERR_INTERNAL);
   m.work[CBG_WORK_IACC] = bp.iacc ? 1 : 0;
 }
 
@@ -4586,29 +4678,44 @@ static void plan_slabs(LocalMul& m) {
   const int nbig = bp.nbig;
   m.slist.reset(m.nslabs);
   const int NK = SLAB_NCLS * slab_kr(bp.R);
-  DBuf<int> counters(2 * NK + SLAB_NCLS);  // counts[NK] | cursor[NK] | class totals
-  CBG_HIP(hipMemsetAsync(counters.p, 0, (2 * NK + SLAB_NCLS) * sizeof(int), s));
+  DBuf<int> counters(2 * NK + SLAB_NCLS + 1);  // counts[NK] | cursor[NK] | class totals | slabs over the large cap
+  CBG_HIP(hipMemsetAsync(counters.p, 0, (2 * NK + SLAB_NCLS + 1) * sizeof(int), s));
   const int rank_span = 1 << bp.plog, rank_min = RANK_SLABS_MIN;
+  // (the caps of launch_slabs' two bitmap classes)
+  const int small_cap = bp.iacc ? SLAB_SMALL_CAP_IA : SLAB_SMALL_CAP;
+  const int large_cap = bp.iacc ? SLAB_LARGE_CAP_IA : SLAB_LARGE_CAP;
   // (CBG_GRANK_MIN, read per call: group slabs of more nonzeros than this run
   // as group rank slabs; -1 none)
   const char* egm = getenv("CBG_GRANK_MIN");
   const int grank_min = egm ? (atoi(egm) < 0 ? INT32_MAX : atoi(egm)) : GRANK_SLABS_MIN;
   hipLaunchKernelGGL(k_slab_count, dim3(nblk(nbig, 256)), dim3(256), NK * sizeof(int), s, nbig, bp.R, bp.nslab.p,
-                     bp.cnt_br.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p);
+                     bp.cnt_br.p, bp.desc.p, small_cap, large_cap, rank_span, rank_min, grank_min, counters.p,
+                     counters.p + 2 * NK + SLAB_NCLS);
   hipLaunchKernelGGL(k_slab_bases, dim3(1), dim3(64), 0, s, bp.R, counters.p, counters.p + NK, counters.p + 2 * NK);
   hipLaunchKernelGGL(k_slab_fill, dim3(nblk(nbig, 256)), dim3(256), 2 * NK * sizeof(int), s, nbig, bp.R,
-                     bp.nslab.p, bp.desc.p, SLAB_SMALL_CAP, rank_span, rank_min, grank_min, counters.p + NK, m.slist.p,
+                     bp.nslab.p, bp.desc.p, small_cap, rank_span, rank_min, grank_min, counters.p + NK, m.slist.p,
                      bp.perm_big, m.B.cp, m.colptr.p,
                      bp.gbm_slot.p, bp.plog, m.A.m, bp.pcoff.p);
   int* ncls_h = reinterpret_cast<int*>(host_stage(STAGE_SLABS));
-  CBG_HIP(hipMemcpyAsync(ncls_h, counters.p + 2 * NK, SLAB_NCLS * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (bp.gbm_next) CBG_HIP(hipMemcpyAsync(ncls_h + SLAB_NCLS, bp.gbm_next, sizeof(int), hipMemcpyDeviceToHost, s));
+  CBG_HIP(hipMemcpyAsync(ncls_h, counters.p + 2 * NK, (SLAB_NCLS + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (bp.gbm_next)
+    CBG_HIP(hipMemcpyAsync(ncls_h + SLAB_NCLS + 1, bp.gbm_next, sizeof(int), hipMemcpyDeviceToHost, s));
   CBG_HIP(hipStreamSynchronize(s));  // host sync 3 of 4: the slab classes' sizes
+  // a check, not a fallback: a slab planned beyond the cap of the kernels about to run
+  // (the symbolic's plan and the host's launch disagree on the verdict) ends the multiply
+  m.work[CBG_WORK_SLAB_OVER_CAP] = ncls_h[SLAB_NCLS];
+  if (ncls_h[SLAB_NCLS] != 0) {
+    m.df.take(counters);
+    m.df.synced = true;
+    throw HipError(std::to_string(ncls_h[SLAB_NCLS]) + " bitmap slabs planned beyond the cap of " +
+                       std::to_string(large_cap) + " nonzeros",
+                   CBG_ERR_INTERNAL);
+  }
   const int* ncls = m.ncls;
   std::memcpy(m.ncls, ncls_h, sizeof(int) * SLAB_NCLS);
   // (CBG_DBG bit 128 hands out slots without storing the bitmaps: the
   // marking pass must run)
-  bp.all_kept = bp.gbm_next && (int64_t)ncls_h[SLAB_NCLS] <= bp.gbm_slots && !(dbg_mask() & 128);
+  bp.all_kept = bp.gbm_next && (int64_t)ncls_h[SLAB_NCLS + 1] <= bp.gbm_slots && !(dbg_mask() & 128);
   m.df.take(counters);
   m.work[bp.all_kept ? CBG_WORK_BITMAP_SMALL_KEPT : CBG_WORK_BITMAP_SMALL_MARK] = ncls[0];
   m.work[bp.all_kept ? CBG_WORK_BITMAP_LARGE_KEPT : CBG_WORK_BITMAP_LARGE_MARK] = ncls[1];

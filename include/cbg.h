@@ -66,7 +66,8 @@ enum {
   CBG_ERR_HIP = 3100,
   CBG_ERR_RCCL = 3101,
   CBG_ERR_OOM = 3102,
-  CBG_ERR_NOTSUPPORTED = 3103
+  CBG_ERR_NOTSUPPORTED = 3103,
+  CBG_ERR_INTERNAL = 3104 /* a check of the library on its own state failed */
 };
 
 /* ---------------- library ---------------- */
@@ -216,7 +217,11 @@ enum {
    * keeps the hops). */
   CBG_WORK_STAGED_MULTIPLIES = 35, /* multiplies that used staged runs */
   CBG_WORK_STAGED_ENTRIES = 36,    /* B entries x panels of the pairs whose bitmap slabs read them */
-  CBG_WORK_N = 37
+  /* bitmap slabs the symbolic planned beyond the cap of the slab kernels the numeric was about
+   * to launch: the library's own check, always 0 (a multiply that counts one fails with
+   * CBG_ERR_INTERNAL before any slab kernel starts) */
+  CBG_WORK_SLAB_OVER_CAP = 37,
+  CBG_WORK_N = 38
 };
 int cbg_last_work_stats(int64_t* counts, int n);
 /* The two thresholds of that preparation: bounds[0] = E, a multiply maps only the A
@@ -224,6 +229,10 @@ int cbg_last_work_stats(int64_t* counts, int n);
  * bounds[1] = F, the (row, f64) records are packed by the first multiply whose big
  * columns carry >= F x nnz(A) flops.  Writes min(n, 2) values, returns 2. */
 int cbg_local_aprep_bounds(int64_t* bounds, int n);
+/* The most nonzeros of a bitmap slab in its two launch classes: out[0], out[1] the small
+ * and the large class where the slabs accumulate f64 values, out[2], out[3] where they
+ * accumulate exact integers in int32 (CBG_WORK_IACC).  Returns 0. */
+int cbg_local_slab_caps(int out[4]);
 /* last call's multiway merges (MergeAll / MultiwayMerge): partial entries in,
  * merged entries out, device ms */
 int cbg_merge_stats(int64_t* entries_in, int64_t* entries_out, double* ms);
