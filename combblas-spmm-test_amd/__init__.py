@@ -90,10 +90,14 @@ EXPORTS = [
     "cbg_grid_connected_components", "cbg_grid_hipmcl", "cbg_last_hipmcl_stats",
     "cbg_tile_spref", "cbg_grid_spref", "cbg_rand_perm", "cbg_spref_sort_bounds", "cbg_last_spref_stats",
     "cbg_grid_hipmcl_prepared", "cbg_grid_nonisolated",
+    "cbg_tile_ewise", "cbg_ewise_bounds", "cbg_last_ewise_stats", "cbg_grid_betwcent", "cbg_last_betwcent_stats",
 ]
 RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT = 0, 1, 2, 3  # cbg_grid_reduce_cols
 _REDS = {"sum": RED_SUM, "plus": RED_SUM, "max": RED_MAX, "maximum": RED_MAX, "sumsq": RED_SUMSQ, "count": RED_COUNT}
-APPLY_POW = 0
+APPLY_POW, APPLY_SET, APPLY_RDIV = 0, 1, 2
+_APPLY = {"pow": APPLY_POW, "set": APPLY_SET, "rdiv": APPLY_RDIV}
+EWISE_MULT, EWISE_FIRST, EWISE_EXCLUDE = 0, 1, 2
+_EWISE = {"mult": EWISE_MULT, "first": EWISE_FIRST, "exclude": EWISE_EXCLUDE}
 
 
 class CHipMclParams(ctypes.Structure):
@@ -108,6 +112,13 @@ class CHipMclPrep(ctypes.Structure):
     _fields_ = [("remove_isolated", ctypes.c_int32), ("randpermute", ctypes.c_int32), ("perm_seed", ctypes.c_uint64)]
 
 
+class CBetwcentParams(ctypes.Structure):
+    """cbg_betwcent_params: roots per batch, algo and exec of the SUMMA"""
+    _fields_ = [("batch", ctypes.c_int64), ("algo", ctypes.c_int32), ("exec", ctypes.c_int32)]
+
+
+# void (*cbg_betwcent_level_fn)(void* user, int64 batch, int64 level, int64 fringe_nnz)
+BETWCENT_LEVEL_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64)
 PERM_SEED = 0x5EED  # HipMCL(randpermute=True) default
 # void (*cbg_hipmcl_iter_fn)(void* user, int64 iter, double chaos, int64 nnz, double ms_expand, ms_prune, ms_inflate)
 HIPMCL_ITER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
@@ -214,6 +225,11 @@ def lib():
         "cbg_tile_spref": ([T, vp, i64, vp, i64, T], i32),
         "cbg_grid_spref": ([vp, T, i64, i64, vp, i64, vp, i64, T], i32),
         "cbg_rand_perm": ([i64, ctypes.c_uint64, vp], i32),
+        "cbg_grid_betwcent": ([vp, T, T, i64, vp, i64, ctypes.POINTER(CBetwcentParams), BETWCENT_LEVEL_FN, vp, vp], i32),
+        "cbg_last_betwcent_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_tile_ewise": ([T, T, i32, T], i32),
+        "cbg_ewise_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_last_ewise_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_spref_sort_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_spref_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_grid_nonisolated": ([vp, T, i64, vp, ctypes.POINTER(i64)], i32),
@@ -361,6 +377,19 @@ class Tile:
         t = Tile()
         _check(lib().cbg_tile_spref(ctypes.byref(self.c), ri.ctypes.data if ri is not None else None, nri,
                                     ci.ctypes.data if ci is not None else None, nci, ctypes.byref(t.c)))
+        return t
+
+    def ewise(self, other, op="mult"):
+        """EWiseMult / SetDifference with a tile of the same shape (SpDCCols.cpp:631-690) -> new tile.
+        op "mult": stored in both, a * b; "first": stored in both, a's value bit for bit (other is a
+        mask); "exclude": stored here and not in other, a's value bit for bit.  other None: the
+        empty tile."""
+        code = _EWISE.get(op, op) if isinstance(op, str) else op
+        if code not in (EWISE_MULT, EWISE_FIRST, EWISE_EXCLUDE):
+            raise CbgError(INVALIDPARAMS, f"ewise: unknown op {op!r} (mult, first, exclude or an EWISE_* code)")
+        t = Tile()
+        _check(lib().cbg_tile_ewise(ctypes.byref(self.c), ctypes.byref(other.c) if other is not None else None,
+                                    int(code), ctypes.byref(t.c)))
         return t
 
     def split_cols(self, cut):
@@ -1031,10 +1060,12 @@ class SpParMat:
         return out[:self.tile.n]
 
     def Apply(self, op, arg):
-        """SpParMat::Apply(bind2nd(exponentiate(), arg)) (op "pow"), in place."""
-        if op != "pow" and not (isinstance(op, int) and op == APPLY_POW):
-            raise CbgError(INVALIDPARAMS, f"Apply: unknown op {op!r} (\"pow\" or APPLY_POW)")
-        _check(lib().cbg_tile_apply(ctypes.byref(self.tile.c), APPLY_POW, float(arg)))
+        """SpParMat::Apply, in place: op "pow" is bind2nd(exponentiate(), arg), "set" v <- arg (arg 1.0:
+        the unit-valued copy a bool matrix is), "rdiv" v <- arg / v (bind1st(divides<double>(), arg))."""
+        code = _APPLY.get(op) if isinstance(op, str) else op
+        if isinstance(code, bool) or not isinstance(code, int) or code not in (APPLY_POW, APPLY_SET, APPLY_RDIV):
+            raise CbgError(INVALIDPARAMS, f"Apply: unknown op {op!r} (pow, set, rdiv or an APPLY_* code)")
+        _check(lib().cbg_tile_apply(ctypes.byref(self.tile.c), code, float(arg)))
 
     def MakeColStochastic(self):
         """MCL.cpp:390-395, in place."""
@@ -1396,6 +1427,91 @@ def spref_stats():
     return dict(entries_in=int(c[0]), entries_out=int(c[1]), sorted_wave=int(c[2]), sorted_lds=int(c[3]),
                 sorted_radix=int(c[4]), cols_monotone=int(c[5]), bytes_recv=int(c[6]), ms_col=ms[0], ms_row=ms[1],
                 ms_sort=ms[2])
+
+
+def ewise_bounds():
+    """[C, L] of Tile.ewise (cbg_ewise_bounds): a work unit's entries of a, and the longest range of
+    b that a unit matches in LDS"""
+    b = (ctypes.c_int64 * 2)()
+    n = lib().cbg_ewise_bounds(b, 2)
+    return [int(x) for x in b[:n]]
+
+
+def ewise_stats():
+    """the last Tile.ewise on this thread (cbg_last_ewise_stats); after BetwCent the sums over all the
+    element-wise calls of that run.  ms: between device events around a call's kernels, the one host
+    readback in their middle included."""
+    c, ms = (ctypes.c_int64 * 7)(), ctypes.c_double()
+    lib().cbg_last_ewise_stats(c, 7, ctypes.byref(ms))
+    return dict(entries_a=int(c[0]), entries_b=int(c[1]), entries_out=int(c[2]), units=int(c[3]),
+                units_none=int(c[4]), units_lds=int(c[5]), units_global=int(c[6]), ms=ms.value)
+
+
+def EWiseMult(A, B, exclude=False):
+    """EWiseMult(A, B, exclude) (SpParMat.cpp:2781-2812): A .* B, or A .* not(B) when exclude; every
+    rank works on its own pair of tiles.  The grids must be the same and the dimensions agree."""
+    if A.grid is not B.grid and not (A.grid is not None and B.grid is not None and A.grid.h == B.grid.h):
+        raise CbgError(GRIDMISMATCH, "EWiseMult: the matrices live on different grids")
+    if (A.gm, A.gn) != (B.gm, B.gn):
+        raise CbgError(DIMMISMATCH, "EWiseMult: the matrices differ in shape")
+    return SpParMat(A.tile.ewise(B.tile, "exclude" if exclude else "mult"), A.grid, A.gm, A.gn)
+
+
+def SetDifference(A, B):
+    """SetDifference(A, B): the entries of A that B does not store, values unchanged"""
+    return EWiseMult(A, B, True)
+
+
+def betwcent_candidates(AT, count):
+    """the reference's choice of roots (BetwCent.cpp:118-146): the first `count` vertices whose column
+    of AT stores something, i.e. the vertices with an out-edge.  Collective; the same list on every rank."""
+    U = AT.copy()
+    U.Apply("set", 1.0)
+    ids, n = np.zeros(max(U.gn, 1), np.int64), ctypes.c_int64()
+    _check(lib().cbg_grid_nonisolated(U.grid.h, ctypes.byref(U.tile.c), U.gn, ids.ctypes.data, ctypes.byref(n)))
+    U.tile.free()
+    return ids[:min(n.value, int(count))].copy()
+
+
+def BetwCent(A, roots, batch, AT=None, on_level=None, algo=DOUBLEBUFF, exec_mode=EXEC_PANEL):
+    """Batched Brandes betweenness centrality (Applications/BetwCent.cpp:148-217) of the graph whose
+    edges i -> j are A's stored entries (values ignored, loops dropped): the sum over `roots` (distinct
+    global vertex ids, the same on every rank) of their dependencies, no halving, the source excluded;
+    `batch` roots at a time; no batch (the last one has len(roots) % batch roots) may hold fewer roots than
+    the grid has columns: INVALIDPARAMS on every rank.  An exception raised by on_level is raised again after
+    the collective has finished.  AT: A's transpose on the same grid (None on a square grid: transposed
+    here).  on_level(batch_index, level, fringe_nnz): called once per level of the forward sweep with
+    the fringe's entries over the whole grid.  -> bc, gn doubles, the same on every rank.  Collective."""
+    if AT is not None and ((AT.gm, AT.gn) != (A.gn, A.gm) or not (AT.grid is A.grid or AT.grid.h == A.grid.h)):
+        raise CbgError(DIMMISMATCH, "BetwCent: AT is not A's transpose on A's grid")
+    if A.gm != A.gn:
+        raise CbgError(DIMMISMATCH, "BetwCent needs a square matrix")
+    r, n = _index_arg(np.asarray(roots, np.int64))
+    bc = np.zeros(max(A.gn, 1), np.float64)
+    prm = CBetwcentParams(int(batch), algo, exec_mode)
+
+    errors = []
+
+    def _cb(user, b, level, nnz):
+        try:
+            on_level(int(b), int(level), int(nnz))
+        except Exception as e:  # noqa: BLE001 -- reported after the collective finishes
+            errors.append(e)
+
+    cb = BETWCENT_LEVEL_FN(_cb) if on_level is not None else BETWCENT_LEVEL_FN()
+    _check(lib().cbg_grid_betwcent(A.grid.h, ctypes.byref(A.tile.c), ctypes.byref(AT.tile.c) if AT is not None else None,
+                                   A.gn, r.ctypes.data, n, ctypes.byref(prm), cb, None, bc.ctypes.data))
+    if errors:
+        raise errors[0]
+    return bc[:A.gn]
+
+
+def betwcent_stats():
+    """the last BetwCent on this rank (cbg_last_betwcent_stats); the times are host ms"""
+    c, ms = (ctypes.c_int64 * 4)(), (ctypes.c_double * 5)()
+    lib().cbg_last_betwcent_stats(c, 4, ms)
+    return dict(batches=int(c[0]), levels=int(c[1]), deepest=int(c[2]), fringe_entries=int(c[3]), ms_forward=ms[0],
+                ms_ewise=ms[1], ms_backward=ms[2], ms_dense=ms[3], ms_total=ms[4])
 
 
 def RemoveIsolated(A):

@@ -45,6 +45,8 @@ int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_par
                 void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters, int64_t* iterations);
 int grid_spref(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
                const int64_t* ci, int64_t nci, cbg_tile& out);
+int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn, const int64_t* roots, int64_t nroots,
+                  const cbg_betwcent_params& P, cbg_betwcent_level_fn fn, void* user, double* bc);
 void rand_perm(int64_t n, uint64_t seed, int64_t* p);
 int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids);
 int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
@@ -690,10 +692,18 @@ int cbg_mcl_moment_bounds(int64_t* bounds, int n) { return cbg::mcl_moment_bound
 
 int cbg_tile_apply(cbg_tile* t, int op, double arg) {
   if (int rc = check_tile(t, true, "tile")) return rc;
-  if (op != CBG_APPLY_POW || arg != arg) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_apply: op is CBG_APPLY_POW, arg a number");
+  if (op < CBG_APPLY_POW || op > CBG_APPLY_RDIV || arg != arg)
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_apply: op is CBG_APPLY_POW, _SET or _RDIV, arg a number");
+  // a compatibility rule (include/cbg.h): op 1 was an unknown op once, and callers probed it with a tile struct
+  // without arrays; the two new functors still answer those calls with INVALIDPARAMS.  Every device tile
+  // libcbg makes holds cp, an empty one too (cp[0] = 0), and val where it has entries
+  if (op != CBG_APPLY_POW && (!t->cp || (t->nnz > 0 && !t->val)))
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_apply: the tile has no arrays (cp, or val of a tile with entries, is NULL)");
   return guard([&] {
     hipStream_t s = default_stream();
-    cbg::tile_apply_pow(*t, arg, s);
+    if (op == CBG_APPLY_POW) cbg::tile_apply_pow(*t, arg, s);
+    else if (op == CBG_APPLY_SET) cbg::tile_apply_set(*t, arg, s);
+    else cbg::tile_apply_rdiv(*t, arg, s);
     CBG_HIP(hipStreamSynchronize(s));
     return CBG_OK;
   });
@@ -842,6 +852,85 @@ int cbg_grid_spref(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, c
     cbg::spref_stats() = cbg::SprefStats{};
     return cbg::grid_spref(g, *local, gm, gn, ri, nri, ci, nci, *out);
   });
+}
+
+// ---------------- sparse element-wise ops ----------------
+int cbg_tile_ewise(const cbg_tile* a, const cbg_tile* b, int op, cbg_tile* out) {
+  if (int rc = check_tile(a, true, "a")) return rc;
+  if (!out) return fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
+  if (op < CBG_EWISE_MULT || op > CBG_EWISE_EXCLUDE)
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_ewise: op is CBG_EWISE_MULT, _FIRST or _EXCLUDE");
+  if (b) {
+    if (int rc = check_tile(b, true, "b")) return rc;
+    if (a->m != b->m || a->n != b->n) return fail(CBG_ERR_DIMMISMATCH, "cbg_tile_ewise: a and b differ in shape");
+  }
+  return guard([&] {
+    cbg::ewise_stats() = cbg::EwiseStats{};
+    cbg::TileGuard o;
+    hipStream_t s = default_stream();
+    cbg::tile_ewise(*a, b, op, o.t, s);
+    CBG_HIP(hipStreamSynchronize(s));
+    CBG_HIP(hipGetLastError());  // a refused launch is this call's failure, not a later one's
+    *out = o.release();
+    return CBG_OK;
+  });
+}
+
+int cbg_ewise_bounds(int64_t* bounds, int n) { return cbg::ewise_bounds(bounds, n); }
+
+int cbg_last_ewise_stats(int64_t* counts, int n, double* ms) {
+  const cbg::EwiseStats& e = cbg::ewise_stats();
+  for (int i = 0; counts && i < n && i < CBG_EWISE_N; ++i) counts[i] = e.counts[i];
+  if (ms) *ms = e.ms;
+  return CBG_EWISE_N;
+}
+
+// ---------------- batched betweenness centrality ----------------
+int cbg_grid_betwcent(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* AT_local, int64_t gn, const int64_t* roots,
+                      int64_t nroots, const cbg_betwcent_params* p, cbg_betwcent_level_fn fn, void* user, double* bc) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(A_local, true, "A");
+  if (!arg && AT_local) arg = check_tile(AT_local, true, "AT");
+  if (!arg && (!p || gn < 0 || nroots < 0 || (nroots > 0 && !roots) || (gn > 0 && !bc)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_betwcent: params, roots and bc are needed, gn and nroots >= 0");
+  if (!arg && (p->batch < 1 || (p->algo != CBG_DOUBLEBUFF && p->algo != CBG_SYNCH) ||
+               (p->exec != CBG_EXEC_PANEL && p->exec != CBG_EXEC_STAGED)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_betwcent: batch >= 1, algo and exec as the SUMMA's");
+  if (!arg) {  // distinct and in range
+    std::vector<int64_t> r(roots, roots + nroots);
+    std::sort(r.begin(), r.end());
+    if (nroots && (r.front() < 0 || r.back() >= gn || std::adjacent_find(r.begin(), r.end()) != r.end()))
+      arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_betwcent: the roots are distinct vertices below gn");
+  }
+  if (!arg && (A_local->nnz >= INT32_MAX || (AT_local && AT_local->nnz >= INT32_MAX)))
+    arg = fail(CBG_ERR_NOTSUPPORTED, "A tiles need nnz < 2^31");
+  int pr = 1, pc = 1;
+  cbg_grid_info(g, nullptr, nullptr, &pr, &pc, nullptr, nullptr);
+  if (!arg && !AT_local && pr != pc)
+    arg = fail(CBG_ERR_NOTSQUARE, "cbg_grid_betwcent: without AT the grid has to be square (the transpose)");
+  if (!arg && nroots > 0) {
+    // the batch's columns are spread over the grid's columns: every grid column needs one, so that no rank
+    // runs the SUMMA on a block of no columns.  The last batch is the narrowest.
+    const int64_t last = nroots % p->batch ? nroots % p->batch : std::min<int64_t>(p->batch, nroots);
+    if (last < pc)
+      arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_betwcent: a batch (the last one: nroots % batch roots) has fewer roots "
+                                        "than the grid has columns");
+  }
+  // every check above precedes any device work; the code is agreed over the grid
+  return grid_call(g, arg, [&] {
+    cbg::thread_stats() = cbg::LocalStats{};
+    cbg::merge_stats() = cbg::MergeStats{};
+    cbg::spref_stats() = cbg::SprefStats{};
+    cbg::ewise_stats() = cbg::EwiseStats{};
+    return cbg::grid_betwcent(g, *A_local, AT_local, gn, roots, nroots, *p, fn, user, bc);
+  });
+}
+
+int cbg_last_betwcent_stats(int64_t* counts, int n, double* ms) {
+  const cbg::BetwcentStats& b = cbg::betwcent_stats();
+  for (int i = 0; counts && i < n && i < CBG_BC_N; ++i) counts[i] = b.counts[i];
+  for (int i = 0; ms && i < CBG_BC_MS_N; ++i) ms[i] = b.ms[i];
+  return CBG_BC_N;
 }
 
 int cbg_rand_perm(int64_t n, uint64_t seed, int64_t* p) {

@@ -443,6 +443,30 @@ void spref_sort_columns(cbg_tile& t, hipStream_t s);  // rows ascending in every
 void tile_spref(const cbg_tile& T, const int64_t* ri, int64_t nri, const int64_t* ci, int64_t nci, cbg_tile& out,
                 hipStream_t s);
 
+// sparse element-wise ops (cbg_ewise.hip)
+struct EwiseStats {
+  int64_t counts[CBG_EWISE_N] = {};
+  double ms = 0;
+};
+EwiseStats& ewise_stats();  // the calling thread's; reset by cbg_tile_ewise
+int ewise_bounds(int64_t* bounds, int n);
+// b == NULL counts as the empty tile; a and b device tiles of equal shape (a == b allowed)
+void tile_ewise(const cbg_tile& a, const cbg_tile* b, int op, cbg_tile& out, hipStream_t s);
+// SpParMat::Apply's value functors beside the power (cbg_ewise.hip): v <- arg, v <- arg / v
+void tile_apply_set(cbg_tile& t, double arg, hipStream_t s);
+void tile_apply_rdiv(cbg_tile& t, double arg, hipStream_t s);
+
+// BetwCent's dense block (cbg_ewise.hip): column-major, lm rows per column; t's columns index it
+void dense_fill(double* d, int64_t n, double v, hipStream_t s);
+void dense_scale_tile(cbg_tile& t, const double* bcu, int64_t lm, hipStream_t s);       // t(i, j) *= bcu(i, j)
+void dense_add_tile(const cbg_tile& t, double* bcu, int64_t lm, hipStream_t s);         // bcu(i, j) += t(i, j)
+void dense_row_sums(const double* bcu, int64_t lm, int64_t ln, double* out, hipStream_t s);
+struct BetwcentStats {
+  int64_t counts[CBG_BC_N] = {};
+  double ms[CBG_BC_MS_N] = {};
+};
+BetwcentStats& betwcent_stats();
+
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);
 void store_probe(int64_t bytes, int width);

@@ -128,8 +128,11 @@ void read_words(const int64_t* a, const int64_t* b, const int64_t* c, int64_t* d
 // t.val stay NULL for the caller, who owns t (a TileGuard).  The stream is synchronised
 // for the readback of nzc; the kernel that fills jc and cp is then queued on s, and its
 // temporaries wait in df: the caller synchronises s and sets df.synced.
+// extra (may be NULL): nextra more device words that land in extra_host with that readback
+// (a caller that lays the entries out itself reads its nnz here: one copy, one wait).
 void compact_columns(int64_t m, int64_t n, int64_t nnz, int64_t nslots, const int32_t* ids, const int64_t* off,
-                     cbg_tile& t, hipStream_t s, DeferredFree& df);
+                     cbg_tile& t, hipStream_t s, DeferredFree& df, const int64_t* extra = nullptr,
+                     int64_t* extra_host = nullptr, int nextra = 0);
 
 // Layer b.  len[i] (device, nslots values) = the entries slot i will hold;
 // emit(i, dst, oir, oval) is called by all 64 lanes of slot i's wave when len[i] > 0 and

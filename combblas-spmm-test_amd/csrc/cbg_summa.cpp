@@ -2079,6 +2079,177 @@ int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_h
   return CBG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Batched betweenness centrality (Applications/BetwCent.cpp:148-217): see include/cbg.h.
+// The multiplies are the SUMMA's, the fringe comes from grid_spref, nsp grows through
+// merge_tiles, and the masks are tile_ewise; the dense block and its three kernels are in
+// cbg_ewise.hip.  Every local step ends in an agreement, like the collectives it sits between.
+// ---------------------------------------------------------------------------
+BetwcentStats& betwcent_stats() {
+  static thread_local BetwcentStats s;
+  return s;
+}
+
+int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn, const int64_t* roots, int64_t nroots,
+                  const cbg_betwcent_params& P, cbg_betwcent_level_fn fn, void* user, double* bc) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  check_usable(g);
+  BetwcentStats& st = betwcent_stats();
+  st = BetwcentStats{};
+  const auto t_all = clk::now();
+  hipStream_t cs = g->compute;
+  int64_t roff = 0, coff = 0;
+  int rc = !tile_place(g, A, gn, gn, &roff, &coff) || (AT && !tile_place(g, *AT, gn, gn, &roff, &coff))
+               ? (int)CBG_ERR_DIMMISMATCH
+           : (!AT && g->pr != g->pc) ? (int)CBG_ERR_NOTSQUARE
+                                     : (int)CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  // a local step: timed into st.ms[what], its code agreed
+  auto local = [&](int what, const std::function<void()>& f) {
+    const auto t0 = clk::now();
+    const int r = step([&] {
+      f();
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    if (what >= 0) st.ms[what] += ms_since(t0);
+    return agree(g, r);
+  };
+  // every stored entry is `true`: unit-valued copies without loops
+  auto unit_noloops = [&](const cbg_tile& X, cbg_tile& out) {
+    TileGuard c;
+    const int r = local(-1, [&] {
+      tile_slice_cols(X, 0, X.n, c.t, cs);
+      tile_apply_set(c.t, 1.0, cs);
+    });
+    return r ? r : grid_remove_loops(g, c.t, gn, gn, out, nullptr);
+  };
+  TileGuard Au, ATu;
+  if ((rc = unit_noloops(A, Au.t))) return rc;
+  if (AT) {
+    if ((rc = unit_noloops(*AT, ATu.t))) return rc;
+  } else if ((rc = grid_transpose(g, Au.t, ATu.t))) {
+    return rc;
+  }
+  int64_t r0 = 0, r1 = 0;
+  block_span(gn, g->pr, g->prow, r0, r1);
+  const int64_t lm = r1 - r0, lmax = gn - (int64_t)(g->pr - 1) * (gn / g->pr);  // the last block is the longest
+  std::vector<double> acc;
+  if ((rc = agree(g, step([&] { acc.assign((size_t)std::max<int64_t>(gn, 1), 0.0); })))) return rc;
+
+  for (int64_t b0 = 0, bi = 0; b0 < nroots; b0 += P.batch, ++bi) {
+    const int64_t nb = std::min<int64_t>(P.batch, nroots - b0);
+    int64_t c0 = 0, c1 = 0;
+    block_span(nb, g->pc, g->pcol, c0, c1);
+    const int64_t ln = c1 - c0;
+    // fringe = AT(:, batch); nsp = 1 at (root k, column k)
+    TileGuard fringe, nsp;
+    if ((rc = grid_spref(g, ATu.t, gn, gn, nullptr, 0, roots + b0, nb, fringe.t))) return rc;
+    rc = local(-1, [&] {
+      std::vector<int64_t> cp{0};
+      std::vector<int32_t> jc, ir;
+      for (int64_t k = c0; k < c1; ++k)
+        if (roots[b0 + k] >= r0 && roots[b0 + k] < r1) {
+          jc.push_back((int32_t)(k - c0));
+          ir.push_back((int32_t)(roots[b0 + k] - r0));
+          cp.push_back((int64_t)jc.size());
+        }
+      const std::vector<double> one(jc.size(), 1.0);
+      const int64_t e = (int64_t)jc.size();
+      tile_alloc_device(nsp.t, lm, ln, e, e);
+      if (e) {
+        CBG_HIP(hipMemcpyAsync(nsp.t.cp, cp.data(), sizeof(int64_t) * (e + 1), hipMemcpyHostToDevice, cs));
+        CBG_HIP(hipMemcpyAsync(nsp.t.jc, jc.data(), sizeof(int32_t) * e, hipMemcpyHostToDevice, cs));
+        CBG_HIP(hipMemcpyAsync(nsp.t.ir, ir.data(), sizeof(int32_t) * e, hipMemcpyHostToDevice, cs));
+        CBG_HIP(hipMemcpyAsync(nsp.t.val, one.data(), sizeof(double) * e, hipMemcpyHostToDevice, cs));
+        CBG_HIP(hipStreamSynchronize(cs));  // the host vectors end with this step
+      }
+    });
+    if (rc) return rc;
+
+    // ---- forward: the levels of the breadth-first search, path counts as values
+    std::vector<TileGuard> levels;
+    for (int64_t level = 1;; ++level) {
+      int64_t fnnz = fringe.t.nnz;
+      if ((rc = agree(g, step([&] { allreduce_sum_i64(g, &fnnz); })))) return rc;
+      if (fnnz == 0) break;
+      st.counts[CBG_BC_LEVELS] += 1;
+      st.counts[CBG_BC_DEEPEST] = std::max(st.counts[CBG_BC_DEEPEST], level);
+      st.counts[CBG_BC_FRINGE_ENTRIES] += fnnz;
+      if (fn) fn(user, bi, level, fnnz);
+      rc = local(CBG_BC_MS_EWISE, [&] {  // nsp += fringe: the fringe holds none of nsp's positions
+        if (fringe.t.nnz == 0) return;
+        TileGuard sum;
+        if (nsp.t.nnz == 0) tile_slice_cols(fringe.t, 0, fringe.t.n, sum.t, cs);
+        else merge_tiles({nsp.t, fringe.t}, lm, ln, CBG_PLUS_TIMES, sum.t, cs);
+        nsp = std::move(sum);
+      });
+      if (rc) return rc;
+      levels.push_back(std::move(fringe));
+      TileGuard prod;
+      const auto t0 = clk::now();
+      if ((rc = summa_spgemm(g, ATu.t, levels.back().t, gn, gn, CBG_PLUS_TIMES, P.algo, P.exec, prod.t))) return rc;
+      st.ms[CBG_BC_MS_FORWARD] += ms_since(t0);
+      if ((rc = local(CBG_BC_MS_EWISE, [&] { tile_ewise(prod.t, &nsp.t, CBG_EWISE_EXCLUDE, fringe.t, cs); }))) return rc;
+    }
+
+    // ---- backward: the dependencies, from the last level down to level 1
+    TileGuard inv;
+    DBuf<double> bcu, rs;
+    rc = local(CBG_BC_MS_DENSE, [&] {
+      tile_slice_cols(nsp.t, 0, nsp.t.n, inv.t, cs);
+      tile_apply_rdiv(inv.t, 1.0, cs);
+      bcu.reset((size_t)std::max<int64_t>(lm * ln, 1));
+      rs.reset((size_t)std::max<int64_t>(lm, 1));
+      dense_fill(bcu.p, lm * ln, 1.0, cs);
+    });
+    if (rc) return rc;
+    for (int64_t j = (int64_t)levels.size() - 1; j >= 1; --j) {
+      TileGuard w, prod;
+      if ((rc = local(CBG_BC_MS_EWISE, [&] { tile_ewise(inv.t, &levels[j].t, CBG_EWISE_FIRST, w.t, cs); }))) return rc;
+      if ((rc = local(CBG_BC_MS_DENSE, [&] { dense_scale_tile(w.t, bcu.p, lm, cs); }))) return rc;
+      const auto t0 = clk::now();
+      if ((rc = summa_spgemm(g, Au.t, w.t, gn, gn, CBG_PLUS_TIMES, P.algo, P.exec, prod.t))) return rc;
+      st.ms[CBG_BC_MS_BACKWARD] += ms_since(t0);
+      TileGuard scaled;
+      rc = local(CBG_BC_MS_EWISE, [&] {
+        TileGuard masked;
+        tile_ewise(prod.t, &levels[j - 1].t, CBG_EWISE_FIRST, masked.t, cs);
+        tile_ewise(masked.t, &nsp.t, CBG_EWISE_MULT, scaled.t, cs);
+      });
+      if (rc) return rc;
+      if ((rc = local(CBG_BC_MS_DENSE, [&] { dense_add_tile(scaled.t, bcu.p, lm, cs); }))) return rc;
+    }
+
+    // ---- bc += row sums of bcu: this rank's columns, then the grid row's ranks in rank order,
+    // then every grid row's block to every rank
+    rc = local(CBG_BC_MS_DENSE, [&] {
+      std::vector<double> part((size_t)std::max<int64_t>(lmax, 1), 0.0);
+      dense_row_sums(bcu.p, lm, ln, rs.p, cs);
+      if (lm) CBG_HIP(hipMemcpyAsync(part.data(), rs.p, sizeof(double) * lm, hipMemcpyDeviceToHost, cs));
+      CBG_HIP(hipStreamSynchronize(cs));
+      std::vector<double> row((size_t)g->pc * part.size()), col((size_t)g->pr * part.size());
+      allgather_bytes(g, COMM_ROW, part.data(), row.data(), sizeof(double) * lmax);
+      for (int64_t i = 0; i < lmax; ++i) {
+        double s = 0.0;
+        for (int q = 0; q < g->pc; ++q) s += row[(size_t)q * lmax + i];
+        part[i] = s;
+      }
+      allgather_bytes(g, COMM_COL, part.data(), col.data(), sizeof(double) * lmax);
+      for (int q = 0; q < g->pr; ++q) {
+        int64_t a = 0, b = 0;
+        block_span(gn, g->pr, q, a, b);
+        for (int64_t i = a; i < b; ++i) acc[i] += col[(size_t)q * lmax + (i - a)];
+      }
+    });
+    if (rc) return rc;
+    st.counts[CBG_BC_BATCHES] += 1;
+  }
+  for (int64_t v = 0; v < gn; ++v) bc[v] = acc[v] - (double)nroots;
+  st.ms[CBG_BC_MS_TOTAL] = ms_since(t_all);
+  return CBG_OK;
+}
+
 }  // namespace cbg
 
 extern "C" int cbg_get_unique_id(void* id) {

@@ -527,13 +527,30 @@ __global__ void k_compact_columns(int64_t nslots, const int32_t* __restrict__ id
   if (i < nslots) put_column(i, nslots, ids, off, pos, jc, cp);
 }
 
+__global__ void k_gather_extra(const int64_t* __restrict__ nzc, const int64_t* __restrict__ extra, int n,
+                               int64_t* __restrict__ out) {
+  out[0] = *nzc;
+  for (int i = 0; i < n; ++i) out[1 + i] = extra[i];
+}
+
 void compact_columns(int64_t m, int64_t n, int64_t nnz, int64_t nslots, const int32_t* ids, const int64_t* off,
-                     cbg_tile& t, hipStream_t s, DeferredFree& df) {
+                     cbg_tile& t, hipStream_t s, DeferredFree& df, const int64_t* extra, int64_t* extra_host,
+                     int nextra) {
   DBuf<int64_t> pos(nslots + 1);
   scan_nonempty(off, pos.p, nslots, s, &df);
   int64_t nzc = 0;
-  CBG_HIP(hipMemcpyAsync(&nzc, pos.p + nslots, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  CBG_HIP(hipStreamSynchronize(s));
+  if (extra && nextra > 0) {  // the caller's words ride on the readback of nzc
+    DBuf<int64_t> words(1 + nextra);
+    std::vector<int64_t> h(1 + nextra);
+    hipLaunchKernelGGL(k_gather_extra, dim3(1), dim3(1), 0, s, pos.p + nslots, extra, nextra, words.p);
+    CBG_HIP(hipMemcpyAsync(h.data(), words.p, sizeof(int64_t) * (1 + nextra), hipMemcpyDeviceToHost, s));
+    CBG_HIP(hipStreamSynchronize(s));
+    nzc = h[0];
+    std::copy(h.begin() + 1, h.end(), extra_host);
+  } else {
+    CBG_HIP(hipMemcpyAsync(&nzc, pos.p + nslots, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    CBG_HIP(hipStreamSynchronize(s));
+  }
   t.m = m;
   t.n = n;
   t.nnz = nnz;

@@ -621,6 +621,10 @@ class SpParMat {
   }
   // SpParMat::Apply(bind2nd(exponentiate(), power)) (Operations.h:140-143), in place
   void ApplyPow(double power) { cbg_abort_on(cbg_tile_apply(spSeq->tile(), CBG_APPLY_POW, power), "Apply"); }
+  // Apply with a constant (every stored entry becomes v: the bool copy of the reference is v = 1) and with
+  // bind1st(divides<double>(), v) (BetwCent.cpp:192)
+  void ApplySet(double v) { cbg_abort_on(cbg_tile_apply(spSeq->tile(), CBG_APPLY_SET, v), "Apply"); }
+  void ApplyRDiv(double v) { cbg_abort_on(cbg_tile_apply(spSeq->tile(), CBG_APPLY_RDIV, v), "Apply"); }
   // SpParMat::RemoveLoops / AddLoops (SpParMat.cpp:3257-3335); loopvals: the vector's global values
   IT RemoveLoops() {
     cbg_tile t{};
@@ -924,6 +928,45 @@ std::vector<IT> HipMCL(SpParMat<IT, NT, DER>& A, HipMCLParam& param) {
   }
   param.iterations = (int)its;
   return std::vector<IT>(lab.begin(), lab.begin() + A.getncol());
+}
+
+// EWiseMult(A, B, exclude) (SpParMat.cpp:2781-2812): A .* B, or A .* not(B) when exclude: every rank
+// works on its own pair of tiles (cbg_tile_ewise).  Grids and dimensions must agree, as the reference asks.
+template <typename IT, typename NT, typename DER>
+SpParMat<IT, NT, DER> EWiseMult(const SpParMat<IT, NT, DER>& A, const SpParMat<IT, NT, DER>& B, bool exclude) {
+  if (A.commGrid->handle() != B.commGrid->handle()) cbg_abort_on(CBG_ERR_GRIDMISMATCH, "EWiseMult: grids differ");
+  if (A.getnrow() != B.getnrow() || A.getncol() != B.getncol()) cbg_abort_on(CBG_ERR_DIMMISMATCH, "EWiseMult");
+  cbg_tile t{};
+  cbg_abort_on(cbg_tile_ewise(A.spSeq->tile(), B.spSeq->tile(), exclude ? CBG_EWISE_EXCLUDE : CBG_EWISE_MULT, &t), "EWiseMult");
+  return SpParMat<IT, NT, DER>(new DER(t), A.commGrid, A.getnrow(), A.getncol());
+}
+// SetDifference(A, B): the entries of A that B does not store, values unchanged
+template <typename IT, typename NT, typename DER>
+SpParMat<IT, NT, DER> SetDifference(const SpParMat<IT, NT, DER>& A, const SpParMat<IT, NT, DER>& B) {
+  return EWiseMult(A, B, true);
+}
+
+// Batched betweenness centrality (Applications/BetwCent.cpp:148-217, cbg_grid_betwcent): bc of every
+// vertex summed over `roots` (distinct global vertex ids, the same on every rank), `batch` of them at
+// a time; A(i, j) stored = an edge i -> j, values ignored, loops dropped.  AT: A's transpose on the
+// same grid, or NULL on a square grid.  levels (may be NULL): the fringe's entries of every level.
+// No batch -- the last one has roots.size() % batch roots -- may hold fewer roots than the grid has
+// columns (CBG_ERR_INVALIDPARAMS on every rank before any device work).
+template <typename IT, typename NT, typename DER>
+std::vector<double> BetwCent(SpParMat<IT, NT, DER>& A, const std::vector<IT>& roots, int64_t batch,
+                             SpParMat<IT, NT, DER>* AT = nullptr, std::vector<int64_t>* levels = nullptr) {
+  const std::vector<int64_t> r(roots.begin(), roots.end());
+  const int64_t none = 0;
+  const cbg_betwcent_params p = {batch, CBG_DOUBLEBUFF, CBG_EXEC_PANEL};
+  auto fn = [](void* user, int64_t, int64_t, int64_t nnz) {
+    if (user) static_cast<std::vector<int64_t>*>(user)->push_back(nnz);
+  };
+  std::vector<double> bc((size_t)std::max<int64_t>(A.getncol(), 1));
+  cbg_abort_on(cbg_grid_betwcent(A.commGrid->handle(), A.spSeq->tile(), AT ? AT->spSeq->tile() : nullptr, A.getncol(),
+                                 r.empty() ? &none : r.data(), (int64_t)r.size(), &p, fn, levels, bc.data()),
+               "BetwCent");
+  bc.resize((size_t)A.getncol());
+  return bc;
 }
 
 // BlockSpGEMM (BlockSpGEMM.h:14-131): C = A*B block by block, A split into br

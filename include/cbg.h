@@ -426,7 +426,16 @@ int cbg_mcl_moment_bounds(int64_t* bounds, int n);
 /* SpParMat::Apply (SpParMat.h Apply(unop)), in place on a device tile.  CBG_APPLY_POW is
  * exponentiate (Operations.h:140-143): arg == 2.0 is computed as v * v (exact; HipMCL's
  * default inflation), any other arg through the device pow. */
-enum { CBG_APPLY_POW = 0 };
+enum {
+  CBG_APPLY_POW = 0,
+  CBG_APPLY_SET = 1, /* v <- arg: the unit-valued copy that a bool matrix is in the reference (arg 1.0) */
+  CBG_APPLY_RDIV = 2 /* v <- arg / v: bind1st(divides<double>(), arg) (BetwCent.cpp:192); arg / 0 = inf */
+};
+/* any other op, or a NaN arg: CBG_ERR_INVALIDPARAMS.  A compatibility rule: CBG_APPLY_SET and CBG_APPLY_RDIV
+ * also refuse, with the same code and before any device work, a tile struct without its arrays (cp NULL, or
+ * val NULL with nnz > 0).  Ops 1 and 2 were unknown before these functors existed, and callers that probed
+ * "an unknown op" with such a struct keep their answer; CBG_APPLY_POW and the other entry points take the
+ * struct as before.  Every device tile libcbg produces holds cp, an empty one too. */
 int cbg_tile_apply(cbg_tile* t, int op, double arg);
 /* MakeColStochastic (MCL.cpp:390-395), in place, collective along the grid column:
  * inv = (sum == 0) ? DBL_MAX : 1.0 / sum (safemultinv, Operations.h:103-110), then
@@ -537,6 +546,87 @@ int cbg_tile_spref(const cbg_tile* t, const int64_t* ri, int64_t nri, const int6
  * A new local block of 2^31 or more rows or columns: CBG_ERR_NOTSUPPORTED. */
 int cbg_grid_spref(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
                    const int64_t* ci, int64_t nci, cbg_tile* out);
+
+/* ---------------- sparse element-wise ops ---------------- */
+/* EWiseMult / SetDifference of two tiles (Friends.h:744-1030, SpDCCols.cpp:631-690; SpParMat's
+ * EWiseMult, SpParMat.cpp:2781-2812, is this on every rank's pair of tiles). */
+enum {
+  CBG_EWISE_MULT = 0,   /* EWiseMult(A, B, false): stored in both; value a * b (one rounding) */
+  CBG_EWISE_FIRST = 1,  /* the same structure; value a, bit for bit (B is a mask: the reference's
+                           EWiseMult with a bool-valued B, as BetwCent uses its bfs levels) */
+  CBG_EWISE_EXCLUDE = 2 /* SetDifference / EWiseMult(A, B, true): stored in A and not in B;
+                           value a, bit for bit */
+};
+/* a, b: device tiles of equal m x n (else CBG_ERR_DIMMISMATCH); a == b is allowed.  An unknown
+ * op, or a NULL a or out: CBG_ERR_INVALIDPARAMS before any device work.  b == NULL or an empty b:
+ * the empty tile for MULT / FIRST, a copy of a for EXCLUDE.  out is valid DCSC (rows ascending, a
+ * column left with no entry leaves jc, 64-bit offsets); explicit zeros, -0.0 and NaN payloads of
+ * a survive FIRST and EXCLUDE unchanged.
+ * The work unit is a (stored column of a, chunk of at most C of its entries), so a few very
+ * long columns still fill the device.  A unit searches b's column for the rows its chunk
+ * spans and matches inside that range: in LDS where the range holds at most L row ids, else by
+ * a binary search per entry in global memory. */
+int cbg_tile_ewise(const cbg_tile* a, const cbg_tile* b, int op, cbg_tile* out);
+/* bounds[0] = C, bounds[1] = L for i < min(n, 2); returns 2 */
+int cbg_ewise_bounds(int64_t* bounds, int n);
+/* the last cbg_tile_ewise on this thread: entries of a, of b and of out, units, and the units of
+ * each matching class (nothing of b in the chunk's rows, matched in LDS, matched in global
+ * memory).  counts[i] for i < min(n, CBG_EWISE_N); *ms (may be NULL): ms between two device events
+ * around the call's kernels.  That span holds the one host readback in the middle (the totals, before
+ * the output is allocated), so it is the op's time on the stream, not the sum of its kernels' times.
+ * A call answered without a kernel (an empty operand) has no units.  After cbg_grid_betwcent the
+ * figures are SUMS over all the element-wise calls that run made (it resets them at its start).
+ * Returns CBG_EWISE_N. */
+enum {
+  CBG_EWISE_ENTRIES_A = 0,
+  CBG_EWISE_ENTRIES_B = 1,
+  CBG_EWISE_ENTRIES_OUT = 2,
+  CBG_EWISE_UNITS = 3,
+  CBG_EWISE_CLASS0 = 4, /* + c: no range, LDS, global */
+  CBG_EWISE_N = 7
+};
+int cbg_last_ewise_stats(int64_t* counts, int n, double* ms);
+
+/* ---------------- batched betweenness centrality (Applications/BetwCent.cpp:148-217) ---------------- */
+/* Brandes' algorithm as a breadth-first search over a matrix of frontiers, `batch` roots at a time
+ * (the last batch may be shorter, down to the number of the grid's columns; the reference rounds the
+ * count instead).  A(i, j) stored = an edge
+ * i -> j of the gn-vertex graph; stored values are ignored (every stored entry is `true`): the loop
+ * works on unit-valued copies without loops (CBG_APPLY_SET, cbg_grid_remove_loops).  Dropping the
+ * loops is this library's deviation: the reference lets a root's loop put the root into its own
+ * first fringe.  AT_local: A's transpose in the same layout; NULL on a square grid: cbg_grid_transpose;
+ * NULL on any other grid: CBG_ERR_NOTSQUARE.  roots: HOST, nroots distinct global vertex ids below gn,
+ * the same on every rank; a repeated or outside one, batch < 1, a bad algo / exec or a NULL bc:
+ * CBG_ERR_INVALIDPARAMS on every rank before any device work.  A batch's columns are spread over the
+ * grid's columns, and every grid column needs at least one: a batch with fewer roots than the grid has
+ * columns -- the last one, of nroots % batch roots, is the narrowest -- is refused the same way (on a
+ * 1 x 1 or pr x 1 grid every batch passes; on a grid of pc columns choose nroots % batch == 0 or >= pc).
+ * Per batch: fringe = AT(:, batch) (cbg_grid_spref); nsp = 1 at (root k, column k); while the fringe
+ * is non-empty over the grid: nsp += fringe, the fringe is kept as that level, fringe = AT * fringe
+ * (the SUMMA, CBG_PLUS_TIMES), fringe = fringe without nsp's positions (CBG_EWISE_EXCLUDE).  Then
+ * nspInv = 1 / nsp, a dense block bcu of ones, and from the last level down to level 1:
+ * w = nspInv at that level's positions times bcu there, product = A * w masked by the level before
+ * and multiplied by nsp, bcu += product.  bc += row sums of bcu (summed along the batch in column
+ * order, the partial sums of a grid row's ranks added in rank order); after the last batch
+ * bc -= nroots.  Path counts are doubles: exact below 2^53 (the reference's int overflows at 2^31).
+ * fn (may be NULL): called on every rank once per level with the batch's index, the level (from 1)
+ * and the fringe's entries over the whole grid.  bc: HOST, gn doubles, the same on every rank. */
+typedef struct cbg_betwcent_params {
+  int64_t batch;
+  int32_t algo, exec;
+} cbg_betwcent_params;
+typedef void (*cbg_betwcent_level_fn)(void* user, int64_t batch, int64_t level, int64_t fringe_nnz);
+int cbg_grid_betwcent(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* AT_local, int64_t gn,
+                      const int64_t* roots, int64_t nroots, const cbg_betwcent_params* p, cbg_betwcent_level_fn fn,
+                      void* user, double* bc);
+/* the last cbg_grid_betwcent on this rank: batches, levels (summed over the batches), the deepest
+ * level, fringe entries (over the grid, summed over the levels); ms (may be NULL, CBG_BC_MS_N host
+ * times): forward multiplies, element-wise ops, backward multiplies, dense ops, total.
+ * counts[i] for i < min(n, CBG_BC_N); returns CBG_BC_N. */
+enum { CBG_BC_BATCHES = 0, CBG_BC_LEVELS = 1, CBG_BC_DEEPEST = 2, CBG_BC_FRINGE_ENTRIES = 3, CBG_BC_N = 4 };
+enum { CBG_BC_MS_FORWARD = 0, CBG_BC_MS_EWISE = 1, CBG_BC_MS_BACKWARD = 2, CBG_BC_MS_DENSE = 3, CBG_BC_MS_TOTAL = 4,
+       CBG_BC_MS_N = 5 };
+int cbg_last_betwcent_stats(int64_t* counts, int n, double* ms);
 
 /* p (HOST, n int64) = the stable argsort of key[i] = mix64(seed ^ (i * 0x9E3779B97F4A7C15)), i = 0..n-1
  * (mix64: the finalizer of cbg_tile_digest).  Equal keys keep index order.  Computed on the host.
