@@ -2058,6 +2058,72 @@ __device__ __forceinline__ RowVal a_rowval(const int32_t* __restrict__ irA, cons
   }
 }
 
+// ---- pieces the persistent slab kernels (bitmap, hash, rank, group rank) share
+// A block's first slab is its block index; the later ones come from the launch's
+// queue.  Thread 0 keeps one dequeue in flight: the slab after the next one --
+// issued a slab ahead, so its returning atomic is not waited for at a slab's
+// start.  `slot`: an int of the block's LDS.  No barrier in here: advance() at a
+// slab's top, next() behind the barrier the kernel has anyway.
+struct SlabQueue {
+  int qnext;
+  __device__ __forceinline__ void start(int* queue) {
+    qnext = 0;
+    if (threadIdx.x == 0) qnext = (int)gridDim.x + atomicAdd(queue, 1);
+  }
+  __device__ __forceinline__ void advance(int* queue, int* slot) {
+    if (threadIdx.x == 0) {
+      *slot = qnext;  // the next slab (dequeued during this block's previous slab)
+      qnext = (int)gridDim.x + atomicAdd(queue, 1);
+    }
+  }
+  // the next slab's index in the launch's list (none is left when it is past the list's end);
+  // returned, not written through a reference: that form cost k_num_slab a VGPR
+  static __device__ __forceinline__ int next(const int* slot) { return *slot; }
+};
+// A(:,k)'s run over the panels r .. r1 (a panel group: the first panel's start to
+// the last one's end; one map entry for a single panel)
+__device__ __forceinline__ int2 panel_group_run(const PMap& pm, int r, int r1, int k) {
+  int2 e = pm.at(r, k);
+  if (r1 != r) e.y = pm.at(r1, k).y;
+  return e;
+}
+// vals[0, nout) set to the semiring's identity (int32 sums under IACC)
+template <int SR, bool IA, int BS>
+__device__ __forceinline__ void slab_fill_identity(double* vals, int nout) {
+  if (IA) {
+    const int id = SemI<SR>::identity();
+    int4* v4 = reinterpret_cast<int4*>(vals);
+    for (int j = threadIdx.x; j < (nout + 3) >> 2; j += BS) v4[j] = make_int4(id, id, id, id);
+  } else {  // 16-byte LDS stores (vals is 16-byte aligned, its capacity even): flat to +0.3 % at 22, +2.5 % at 18
+    const double id = Sem<SR>::identity();
+    double2* v2 = reinterpret_cast<double2*>(vals);
+    for (int j = threadIdx.x; j < (nout + 1) >> 1; j += BS) v2[j] = make_double2(id, id);
+  }
+}
+// rows[0, nout) and vals[0, nout), in rank order (C's order), to C at obase: coalesced copies
+template <bool IA, int BS>
+__device__ __forceinline__ void slab_emit_ranked(const int* rows, const double* vals, int nout, int64_t obase,
+                                                 int32_t* __restrict__ out_ir, double* __restrict__ out_val) {
+  for (int j = threadIdx.x; j < nout; j += BS) {
+    st_rows<IA>(&out_ir[obase + j], rows[j]);
+    st_emit(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
+  }
+}
+// one chunk of <= BS B entries staged for block_products: thread t's segment
+// (A run from s, len products, B value bval); returns the chunk's products.
+// The caller's barrier comes after it.
+template <int BS>
+__device__ __forceinline__ int stage_chunk(int s, int len, double bval, int* pref, int* st, double* bv, int* tmp) {
+  const int tid = threadIdx.x;
+  int total;
+  const int ex = block_excl_scan<BS>(len, tmp, &total);
+  pref[tid] = ex;
+  if (tid == BS - 1) pref[BS] = total;
+  st[tid] = seg_stage(s, ex);
+  bv[tid] = bval;
+  return total;
+}
+
 struct RankVal {
   int rank, row;
   double v;
@@ -2172,19 +2238,14 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       if (staged(r) && tid < r.nb) p_ce = pm.at(r.r, p_ir);
   };
   SlabRec rec = list[i];
-  // (thread 0) the dequeue in flight: the slab after the next one -- issued a
-  // slab ahead, so its returning atomic is not waited for at a slab's start
-  int qnext = 0;
-  if (tid == 0) qnext = (int)gridDim.x + atomicAdd(queue, 1);
+  SlabQueue sq;
+  sq.start(queue);
   fetch_words(rec);
   fetch_stage1(rec);
   fetch_stage2(rec);
   while (true) {
     // ---- next work item (its record arrives while this slab fills LDS)
-    if (tid == 0) {
-      tmp[NW + 2] = qnext;  // the next slab (dequeued during this block's previous slab)
-      qnext = (int)gridDim.x + atomicAdd(queue, 1);
-    }
+    sq.advance(queue, tmp + NW + 2);
     const int nout = rec.nout;
     const int lo = rec.lo, hi = rec.hi;
     const int words = rec_words(rec);
@@ -2205,26 +2266,14 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       const int j = 4 * (k * BS + tid);
       if (j < words) *reinterpret_cast<uint4*>(bm + j) = have_bm ? pw[k] : make_uint4(0u, 0u, 0u, 0u);
     }
-    if (IA) {
-      const int id = SemI<SR>::identity();
-      int4* v4 = reinterpret_cast<int4*>(vals);
-      for (int j = tid; j < (nout + 3) >> 2; j += BS) v4[j] = make_int4(id, id, id, id);
-    } else {  // 16-byte LDS stores (CAP is even, vals is 16-byte aligned): flat to +0.3 % at 22, +2.5 % at 18
-      const double id = Sem<SR>::identity();
-      double2* v2 = reinterpret_cast<double2*>(vals);
-      for (int j = tid; j < (nout + 1) >> 1; j += BS) v2[j] = make_double2(id, id);
-    }
+    slab_fill_identity<SR, IA, BS>(vals, nout);
     int total = 0;
     if (pre) {
-      const int len = tid < rec.nb ? p_ce.y - p_ce.x : 0;
-      const int ex = block_excl_scan<BS>(len, tmp, &total);
-      pref[tid] = ex;
-      if (tid == BS - 1) pref[BS] = total;
-      st[tid] = seg_stage(tid < rec.nb ? p_ce.x : 0, ex);
-      bv[tid] = tid < rec.nb ? p_bv : 0.0;
+      const bool in = tid < rec.nb;
+      total = stage_chunk<BS>(in ? p_ce.x : 0, in ? p_ce.y - p_ce.x : 0, in ? p_bv : 0.0, pref, st, bv, tmp);
     }
     __syncthreads();
-    const int inext = tmp[NW + 2];
+    const int inext = SlabQueue::next(tmp + NW + 2);
     const bool has_next = inext < n;
     SlabRec nrec;
     if (has_next) nrec = list[inext];
@@ -2305,11 +2354,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
             }
             bval = valB[p];
           }
-          const int ex = block_excl_scan<BS>(len, tmp, &total);
-          pref[tid] = ex;
-          if (tid == BS - 1) pref[BS] = total;
-          st[tid] = seg_stage(s, ex);
-          bv[tid] = bval;
+          total = stage_chunk<BS>(s, len, bval, pref, st, bv, tmp);
           __syncthreads();
           phase_mark(tmark, 1);
         } else {
@@ -2460,22 +2505,65 @@ __device__ __forceinline__ void build_segids(unsigned short* seg16, int* tmp) {
   }
   __syncthreads();
 }
-// products [0, total) by segment ids: thread t takes t + BS k (consecutive
-// threads, consecutive products: coalesced inside a segment), U in flight
-template <int BS, int U, class L, class A>
-__device__ __forceinline__ void block_products_sid(int total, const unsigned short* seg16, const SegRec* srec,
-                                                   L&& load, A&& apply) {
-  for (int u0 = threadIdx.x; u0 < total; u0 += U * BS) {
-    int sg[U];
+// The rank and group rank slabs stage one B entry per thread; the next slab's
+// entry is fetched into registers while the current slab runs: its row and value
+// first, the run of A(:,row) over the slab's panels r .. r1 a stage later
+struct SlabEntryPrefetch {
+  int ir = 0;
+  double bv = 0.0;
+  int2 ce = make_int2(0, 0);
+  __device__ __forceinline__ void fetch1(const SlabRec& r, const int32_t* __restrict__ irB,
+                                         const double* __restrict__ valB) {
+    if ((int)threadIdx.x < r.nb) {
+      ir = irB[r.p0 + threadIdx.x];
+      bv = valB[r.p0 + threadIdx.x];
+    }
+  }
+  __device__ __forceinline__ void fetch2(const SlabRec& r, const PMap& pm, int r1) {
+    if ((int)threadIdx.x < r.nb) ce = panel_group_run(pm, r.r, r1, ir);
+  }
+};
+// staging of a slab of nb <= BS B entries, RK * BS products at most: segment t =
+// B entry t, its first product at ex; srec[t] written, seg16 zeroed and the heads
+// of the nonempty segments marked at their first product (build_segids follows,
+// behind a barrier); returns the slab's products
+template <int BS, int RK>
+__device__ __forceinline__ int stage_segments(const SlabEntryPrefetch& pf, int nb, unsigned short* seg16,
+                                              SegRec* srec, int* tmp) {
+  const int tid = threadIdx.x;
+  for (int g = tid; g < RK * BS / 8; g += BS) reinterpret_cast<uint4*>(seg16)[g] = make_uint4(0u, 0u, 0u, 0u);
+  const int len = tid < nb ? pf.ce.y - pf.ce.x : 0;
+  int total;
+  const int ex = block_excl_scan<BS>(len, tmp, &total);  // (its barriers order the caller's zeroing and the one above)
+  srec[tid] = SegRec{(tid < nb ? pf.ce.x : 0) - ex, 0, tid < nb ? pf.bv : 0.0};
+  if (len > 0) seg16[ex] = (unsigned short)tid;
+  return total;
+}
+// products [0, total) into registers by their segment ids (thread t: t + BS k,
+// all gathers in flight at once): rows above lo in xr (-1 past total), values in
+// xv (exact integers as int under IACC: fewer VGPRs, more blocks per CU)
+template <int SR, typename VA, bool IA, int BS, int RK>
+__device__ __forceinline__ void gather_products(int total, const unsigned short* seg16, const SegRec* srec,
+                                                const int32_t* __restrict__ irA, const VA* __restrict__ valA,
+                                                int lo, int (&xr)[RK],
+                                                typename std::conditional<IA, int, double>::type (&xv)[RK]) {
+  const int tid = threadIdx.x;
+  int sg[RK];
 #pragma unroll
-    for (int j = 0; j < U; ++j) sg[j] = u0 + j * BS < total ? seg16[u0 + j * BS] : -1;
-    decltype(load(SegRec{}, 0)) x[U];
+  for (int k = 0; k < RK; ++k) {
+    const int u = tid + k * BS;
+    sg[k] = u < total ? seg16[u] : -1;
+  }
 #pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (sg[j] >= 0) x[j] = load(srec[sg[j]], u0 + j * BS);
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (sg[j] >= 0) apply(x[j]);
+  for (int k = 0; k < RK; ++k) {
+    xr[k] = -1;
+    if (sg[k] >= 0) {
+      const SegRec r = srec[sg[k]];
+      const RowVal x = a_rowval<SR, VA>(irA, valA, r.off + tid + k * BS, r.b, lo);
+      xr[k] = x.row;
+      if constexpr (IA) xv[k] = (int)x.v;
+      else xv[k] = x.v;
+    }
   }
 }
 
@@ -2553,14 +2641,14 @@ __global__ __launch_bounds__(BS) void k_num_slab_hash(const SlabRec* __restrict_
       p_bv1 = valB[r.p0 + BS + tid];
     }
   };
-  // A(:,k)'s run over the slab's rows: one map entry, or the first and last
-  // panels' entries of a panel group (rows [lo, hi) span panels r .. r1)
+  // A(:,k)'s run over the slab's rows [lo, hi)
   auto seg_of = [&](const SlabRec& r, int k) -> int2 {
-    const int2 e = pm.at(r.r, k);
-    if (CMLEN) return make_int2(e.x, e.x + e.y);
-    const int r1 = (r.hi - 1) >> plog;
-    if (r1 == r.r) return e;
-    return make_int2(e.x, pm.at(r1, k).y);
+    if constexpr (CMLEN) {
+      const int2 e = pm.at(r.r, k);
+      return make_int2(e.x, e.x + e.y);
+    } else {
+      return panel_group_run(pm, r.r, (r.hi - 1) >> plog, k);
+    }
   };
   auto fetch2 = [&](const SlabRec& r) {
     if (!staged(r)) return;
@@ -2568,17 +2656,12 @@ __global__ __launch_bounds__(BS) void k_num_slab_hash(const SlabRec* __restrict_
     if (PF > 1 && BS + tid < r.nb) p_ce1 = seg_of(r, p_ir1);
   };
   SlabRec rec = list[i];
-  // (thread 0) the dequeue in flight: the slab after the next one -- issued a
-  // slab ahead, so its returning atomic is not waited for at a slab's start
-  int qnext = 0;
-  if (tid == 0) qnext = (int)gridDim.x + atomicAdd(queue, 1);
+  SlabQueue sq;
+  sq.start(queue);
   fetch1(rec);
   fetch2(rec);
   while (true) {
-    if (tid == 0) {
-      tmp[NW + 2] = qnext;  // the next slab (dequeued during this block's previous slab)
-      qnext = (int)gridDim.x + atomicAdd(queue, 1);
-    }
+    sq.advance(queue, tmp + NW + 2);
     const bool pre = staged(rec);
     unsigned long long tmark = wall_clock64();
     {  // 16-byte LDS stores (T is a multiple of 256; vals and keys are 16-byte aligned)
@@ -2590,7 +2673,7 @@ __global__ __launch_bounds__(BS) void k_num_slab_hash(const SlabRec* __restrict_
     }
     __syncthreads();
     phase_mark(tmark, 7);
-    const int inext = tmp[NW + 2];
+    const int inext = SlabQueue::next(tmp + NW + 2);
     const bool has_next = inext < n;
     SlabRec nrec;
     if (has_next) nrec = list[inext];
@@ -2632,12 +2715,7 @@ __global__ __launch_bounds__(BS) void k_num_slab_hash(const SlabRec* __restrict_
         s = ce.x;
         len = ce.y - ce.x;
       }
-      int total;
-      const int ex = block_excl_scan<BS>(len, tmp, &total);
-      pref[tid] = ex;
-      if (tid == BS - 1) pref[BS] = total;
-      st[tid] = seg_stage(s, ex);
-      bv[tid] = bval;
+      const int total = stage_chunk<BS>(s, len, bval, pref, st, bv, tmp);
       __syncthreads();
       phase_mark(tmark, 13);
       if (c == nch - 1 && has_next) fetch1(nrec);
@@ -2719,6 +2797,51 @@ static_assert(SPARSE_SLAB_MAX == 8 * RANK_BS, "segment scan: 8 products per thre
 __device__ __forceinline__ int popc4(const uint4& q) {
   return __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
 }
+// the rank of bit b of a bitmap: its 4-word group's rank + the bits below it
+__device__ __forceinline__ int bitmap_rank(const uint4* bm4, const unsigned short* gpre, int b) {
+  const int wd = b >> 5, g = wd >> 2, j = wd & 3;
+  const uint4 q = bm4[g];
+  const unsigned below = (1u << (b & 31)) - 1u;
+  int x = gpre[g];
+  x += j > 0 ? __popc(q.x) : __popc(q.x & below);
+  if (j >= 1) x += j > 1 ? __popc(q.y) : __popc(q.y & below);
+  if (j >= 2) x += j > 2 ? __popc(q.z) : __popc(q.z & below);
+  if (j >= 3) x += __popc(q.w & below);
+  return x;
+}
+// the first rank of every 4-word group of bm4[0, ng) into gpre (u16, GPT groups
+// per thread, GPT even); returns the total (block-uniform)
+template <int BS, int GPT>
+__device__ __forceinline__ int bitmap_group_ranks(const uint4* bm4, int ng, unsigned short* gpre, int* tmp) {
+  const int tid = threadIdx.x;
+  uint4 q[GPT];
+  int sum = 0;
+#pragma unroll
+  for (int j = 0; j < GPT; ++j) {
+    const int g = tid * GPT + j;
+    q[j] = g < ng ? bm4[g] : make_uint4(0u, 0u, 0u, 0u);
+    sum += popc4(q[j]);
+  }
+  int tot;
+  int run = block_excl_scan<BS>(sum, tmp, &tot);
+  unsigned pk[GPT / 2];
+#pragma unroll
+  for (int j = 0; j < GPT; j += 2) {
+    const unsigned a = (unsigned)run;
+    run += popc4(q[j]);
+    pk[j / 2] = a | ((unsigned)run << 16);
+    run += popc4(q[j + 1]);
+  }
+  if (tid * GPT < ng) {
+    if constexpr (GPT == 2) *reinterpret_cast<unsigned*>(gpre + tid * GPT) = pk[0];
+    else if constexpr (GPT == 4) *reinterpret_cast<uint2*>(gpre + tid * GPT) = make_uint2(pk[0], pk[1]);
+    else {
+#pragma unroll
+      for (int j = 0; j < GPT / 2; ++j) reinterpret_cast<unsigned*>(gpre + tid * GPT)[j] = pk[j];
+    }
+  }
+  return tot;
+}
 template <int SR, int NCAP, int BS, typename VA, bool IA>
 __global__ __launch_bounds__(BS) void k_num_slab_rank(const SlabRec* __restrict__ list, int n,
                                                       int* __restrict__ queue, const int32_t* __restrict__ irB,
@@ -2740,114 +2863,44 @@ __global__ __launch_bounds__(BS) void k_num_slab_rank(const SlabRec* __restrict_
   uint4* bm4 = reinterpret_cast<uint4*>(smem + L::BM_OFF);
   unsigned short* gpre = reinterpret_cast<unsigned short*>(smem + L::GPRE_OFF);
   int* tmp = reinterpret_cast<int*>(smem + L::TMP_OFF);
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / WAVE;
+  const int tid = threadIdx.x;
   int i = blockIdx.x;
   if (i >= n) return;
-  // next slab's staging (one B entry per thread), fetched while this one runs
-  int p_ir = 0;
-  double p_bv = 0.0;
-  int2 p_ce = make_int2(0, 0);
-  auto fetch1 = [&](const SlabRec& r) {
-    if (tid < r.nb) {
-      p_ir = irB[r.p0 + tid];
-      p_bv = valB[r.p0 + tid];
-    }
-  };
-  auto fetch2 = [&](const SlabRec& r) {
-    if (tid < r.nb) p_ce = pm.at(r.r, p_ir);
-  };
+  SlabEntryPrefetch pf;
   SlabRec rec = list[i];
-  // (thread 0) the dequeue in flight: the slab after the next one -- issued a
-  // slab ahead, so its returning atomic is not waited for at a slab's start
-  int qnext = 0;
-  if (tid == 0) qnext = (int)gridDim.x + atomicAdd(queue, 1);
-  fetch1(rec);
-  fetch2(rec);
+  SlabQueue sq;
+  sq.start(queue);
+  pf.fetch1(rec, irB, valB);
+  pf.fetch2(rec, pm, rec.r);
   while (true) {
-    if (tid == 0) {
-      tmp[NW + 2] = qnext;  // the next slab (dequeued during this block's previous slab)
-      qnext = (int)gridDim.x + atomicAdd(queue, 1);
-    }
+    sq.advance(queue, tmp + NW + 2);
     unsigned long long tmark = wall_clock64();
     const int lo = rec.lo, nout = rec.nout;
     const int ng = (((rec.hi - lo + 31) >> 5) + 3) >> 2;
     const int64_t obase = rec.obase;
     for (int g = tid; g < ng; g += BS) bm4[g] = make_uint4(0u, 0u, 0u, 0u);
-    reinterpret_cast<uint4*>(seg16)[tid] = make_uint4(0u, 0u, 0u, 0u);  // 8 products per thread
-    // staging: segment t = B entry t; its first product at ex; heads of the
-    // nonempty segments marked at their first product
-    const int len = tid < rec.nb ? p_ce.y - p_ce.x : 0;
-    int total;
-    const int ex = block_excl_scan<BS>(len, tmp, &total);  // (its barriers order the zeroing above)
-    srec[tid] = SegRec{(tid < rec.nb ? p_ce.x : 0) - ex, 0, tid < rec.nb ? p_bv : 0.0};
-    if (len > 0) seg16[ex] = (unsigned short)tid;
-    const int inext = tmp[NW + 2];
+    const int total = stage_segments<BS, RK>(pf, rec.nb, seg16, srec, tmp);
+    const int inext = SlabQueue::next(tmp + NW + 2);
     const bool has_next = inext < n;
     SlabRec nrec;
     if (has_next) nrec = list[inext];
     __syncthreads();
     build_segids<BS, RK>(seg16, tmp);  // every product's segment
     phase_mark(tmark, 16);
-    // 1. products into registers (thread t: t + BS k), rows marked in the bitmap
+    // 1. products into registers, rows marked in the bitmap
     int xr[RK];
-    typename std::conditional<IA, int, double>::type xv[RK];  // (exact integers as int: fewer VGPRs)
-    {
-      int sg[RK];
+    typename std::conditional<IA, int, double>::type xv[RK];
+    gather_products<SR, VA, IA, BS, RK>((c_dbg & 512) ? 0 : total, seg16, srec, irA, valA, lo, xr, xv);
 #pragma unroll
-      for (int k = 0; k < RK; ++k) {
-        const int u = tid + k * BS;
-        sg[k] = u < total ? seg16[u] : -1;
-      }
-#pragma unroll
-      for (int k = 0; k < RK; ++k) {
-        xr[k] = -1;
-        if (sg[k] >= 0 && !(c_dbg & 512)) {
-          const SegRec r = srec[sg[k]];
-          const RowVal x = a_rowval<SR, VA>(irA, valA, r.off + tid + k * BS, r.b, lo);
-          xr[k] = x.row;
-          if constexpr (IA) xv[k] = (int)x.v;
-          else xv[k] = x.v;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RK; ++k)
-        if (xr[k] >= 0) atomicOr(&bm[xr[k] >> 5], 1u << (xr[k] & 31));
-    }
-    if (has_next) fetch1(nrec);
+    for (int k = 0; k < RK; ++k)
+      if (xr[k] >= 0) atomicOr(&bm[xr[k] >> 5], 1u << (xr[k] & 31));
+    if (has_next) pf.fetch1(nrec, irB, valB);
     __syncthreads();
     phase_mark(tmark, 17);
     // 2. group ranks: thread t owns groups 4t .. 4t+3 (one 8-byte store of 4
     // u16); vals (aliasing the staging, now idle) set to the semiring's identity
-    {
-      if (IA) {
-        const int id = SemI<SR>::identity();
-        int4* v4 = reinterpret_cast<int4*>(vals);
-        for (int j = tid; j < (nout + 3) >> 2; j += BS) v4[j] = make_int4(id, id, id, id);
-      } else {
-        const double id = Sem<SR>::identity();
-        double2* v2 = reinterpret_cast<double2*>(vals);
-        for (int j = tid; j < (nout + 1) >> 1; j += BS) v2[j] = make_double2(id, id);
-      }
-      uint4 q[GPT];
-      int sum = 0;
-#pragma unroll
-      for (int j = 0; j < GPT; ++j) {
-        const int g = tid * GPT + j;
-        q[j] = g < ng ? bm4[g] : make_uint4(0u, 0u, 0u, 0u);
-        sum += popc4(q[j]);
-      }
-      int tot;
-      int run = block_excl_scan<BS>(sum, tmp, &tot);
-      unsigned pk[GPT / 2];
-#pragma unroll
-      for (int j = 0; j < GPT; j += 2) {
-        const unsigned a = (unsigned)run;
-        run += popc4(q[j]);
-        pk[j / 2] = a | ((unsigned)run << 16);
-        run += popc4(q[j + 1]);
-      }
-      *reinterpret_cast<uint2*>(gpre + tid * GPT) = make_uint2(pk[0], pk[1]);
-    }
+    slab_fill_identity<SR, IA, BS>(vals, nout);
+    bitmap_group_ranks<BS, GPT>(bm4, ng, gpre, tmp);
     __syncthreads();
     phase_mark(tmark, 18);
     // 3. accumulate at the ranks (all lookups first, then the atomics); each
@@ -2859,17 +2912,7 @@ __global__ __launch_bounds__(BS) void k_num_slab_rank(const SlabRec* __restrict_
 #pragma unroll
       for (int k = 0; k < RK; ++k) {
         rk[k] = -1;
-        if (xr[k] >= 0) {
-          const int r = xr[k], wd = r >> 5, g = wd >> 2, j = wd & 3;
-          const uint4 q = bm4[g];
-          const unsigned below = (1u << (r & 31)) - 1u;
-          int x = gpre[g];
-          x += j > 0 ? __popc(q.x) : __popc(q.x & below);
-          if (j >= 1) x += j > 1 ? __popc(q.y) : __popc(q.y & below);
-          if (j >= 2) x += j > 2 ? __popc(q.z) : __popc(q.z & below);
-          if (j >= 3) x += __popc(q.w & below);
-          rk[k] = x;
-        }
+        if (xr[k] >= 0) rk[k] = bitmap_rank(bm4, gpre, xr[k]);
       }
       __syncthreads();
       int* rows = reinterpret_cast<int*>(bm);  // [nout] (nout <= NCAP <= SLAB_WORDS)
@@ -2881,17 +2924,11 @@ __global__ __launch_bounds__(BS) void k_num_slab_rank(const SlabRec* __restrict_
           rows[rk[k]] = lo + xr[k];
         }
     }
-    if (has_next) fetch2(nrec);
+    if (has_next) pf.fetch2(nrec, pm, nrec.r);
     __syncthreads();
     phase_mark(tmark, 19);
-    // 4. rows and values in rank order (C's order): coalesced copies
-    if (!(c_dbg & 1024)) {
-      const int* rows = reinterpret_cast<const int*>(bm);
-      for (int j = tid; j < nout; j += BS) {
-        st_rows<IA>(&out_ir[obase + j], rows[j]);
-        st_emit(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
-      }
-    }
+    // 4. C's rows and values
+    if (!(c_dbg & 1024)) slab_emit_ranked<IA, BS>(reinterpret_cast<const int*>(bm), vals, nout, obase, out_ir, out_val);
     if ((c_dbg & 32) && tid == 0) {
       atomicAdd(&g_stat[10], (unsigned long long)total);
       atomicAdd(&g_stat[11], (unsigned long long)nout);
@@ -2945,51 +2982,6 @@ struct SlabGRankLds {
                     G2_OFF % 16 == 0 && ROWS_OFF % 16 == 0 && TMP_OFF % 16 == 0,
                 "group rank slab LDS alignment");
 };
-// the rank of bit b of a bitmap: its 4-word group's rank + the bits below it
-__device__ __forceinline__ int bitmap_rank(const uint4* bm4, const unsigned short* gpre, int b) {
-  const int wd = b >> 5, g = wd >> 2, j = wd & 3;
-  const uint4 q = bm4[g];
-  const unsigned below = (1u << (b & 31)) - 1u;
-  int x = gpre[g];
-  x += j > 0 ? __popc(q.x) : __popc(q.x & below);
-  if (j >= 1) x += j > 1 ? __popc(q.y) : __popc(q.y & below);
-  if (j >= 2) x += j > 2 ? __popc(q.z) : __popc(q.z & below);
-  if (j >= 3) x += __popc(q.w & below);
-  return x;
-}
-// the first rank of every 4-word group of bm4[0, ng) into gpre (u16, GPT groups
-// per thread, GPT even); returns the total (block-uniform)
-template <int BS, int GPT>
-__device__ __forceinline__ int bitmap_group_ranks(const uint4* bm4, int ng, unsigned short* gpre, int* tmp) {
-  const int tid = threadIdx.x;
-  uint4 q[GPT];
-  int sum = 0;
-#pragma unroll
-  for (int j = 0; j < GPT; ++j) {
-    const int g = tid * GPT + j;
-    q[j] = g < ng ? bm4[g] : make_uint4(0u, 0u, 0u, 0u);
-    sum += popc4(q[j]);
-  }
-  int tot;
-  int run = block_excl_scan<BS>(sum, tmp, &tot);
-  unsigned pk[GPT / 2];
-#pragma unroll
-  for (int j = 0; j < GPT; j += 2) {
-    const unsigned a = (unsigned)run;
-    run += popc4(q[j]);
-    pk[j / 2] = a | ((unsigned)run << 16);
-    run += popc4(q[j + 1]);
-  }
-  if (tid * GPT < ng) {
-    if constexpr (GPT == 2) *reinterpret_cast<unsigned*>(gpre + tid * GPT) = pk[0];
-    else if constexpr (GPT == 4) *reinterpret_cast<uint2*>(gpre + tid * GPT) = make_uint2(pk[0], pk[1]);
-    else {
-#pragma unroll
-      for (int j = 0; j < GPT / 2; ++j) reinterpret_cast<unsigned*>(gpre + tid * GPT)[j] = pk[j];
-    }
-  }
-  return tot;
-}
 template <int SR, int NCAP, int BS, int SPANLOG, int PMAX, typename VA, bool IA>
 __global__ __launch_bounds__(BS) void k_num_slab_grank(const SlabRec* __restrict__ list, int n,
                                                        int* __restrict__ queue, int plog,
@@ -3018,47 +3010,23 @@ __global__ __launch_bounds__(BS) void k_num_slab_grank(const SlabRec* __restrict
   const int tid = threadIdx.x;
   int i = blockIdx.x;
   if (i >= n) return;
-  int p_ir = 0;
-  double p_bv = 0.0;
-  int2 p_ce = make_int2(0, 0);
-  auto fetch1 = [&](const SlabRec& r) {
-    if (tid < r.nb) {
-      p_ir = irB[r.p0 + tid];
-      p_bv = valB[r.p0 + tid];
-    }
-  };
-  // A(:,k)'s run over the group's panels r .. r1: the first panel's start to
-  // the last one's end
-  auto fetch2 = [&](const SlabRec& r) {
-    if (tid < r.nb) {
-      const int r1 = (r.hi - 1) >> plog;
-      p_ce = pm.at(r.r, p_ir);
-      if (r1 != r.r) p_ce.y = pm.at(r1, p_ir).y;
-    }
-  };
+  SlabEntryPrefetch pf;
+  auto last_panel = [&](const SlabRec& r) { return (r.hi - 1) >> plog; };  // of the group's panels r .. r1
   SlabRec rec = list[i];
-  int qnext = 0;
-  if (tid == 0) qnext = (int)gridDim.x + atomicAdd(queue, 1);
-  fetch1(rec);
-  fetch2(rec);
+  SlabQueue sq;
+  sq.start(queue);
+  pf.fetch1(rec, irB, valB);
+  pf.fetch2(rec, pm, last_panel(rec));
   while (true) {
-    if (tid == 0) {
-      tmp[NW + 2] = qnext;
-      qnext = (int)gridDim.x + atomicAdd(queue, 1);
-    }
+    sq.advance(queue, tmp + NW + 2);
     unsigned long long tmark = wall_clock64();
     const int lo = rec.lo, nout = rec.nout;
     const int ng1 = (((rec.hi - lo + 1023) >> 10) + 3) >> 2;  // level-1 groups (32 rows a bit, 32 bits a word)
     const int64_t obase = rec.obase;
     for (int g = tid; g < ng1; g += BS) l1q[g] = make_uint4(0u, 0u, 0u, 0u);
     for (int g = tid; g < (nout + 3) >> 2; g += BS) l2q[g] = make_uint4(0u, 0u, 0u, 0u);
-    for (int g = tid; g < PMAX / 8; g += BS) reinterpret_cast<uint4*>(seg16)[g] = make_uint4(0u, 0u, 0u, 0u);
-    const int len = tid < rec.nb ? p_ce.y - p_ce.x : 0;
-    int total;
-    const int ex = block_excl_scan<BS>(len, tmp, &total);  // (its barriers order the zeroing above)
-    srec[tid] = SegRec{(tid < rec.nb ? p_ce.x : 0) - ex, 0, tid < rec.nb ? p_bv : 0.0};
-    if (len > 0) seg16[ex] = (unsigned short)tid;
-    const int inext = tmp[NW + 2];
+    const int total = stage_segments<BS, RK>(pf, rec.nb, seg16, srec, tmp);
+    const int inext = SlabQueue::next(tmp + NW + 2);
     const bool has_next = inext < n;
     SlabRec nrec;
     if (has_next) nrec = list[inext];
@@ -3066,44 +3034,17 @@ __global__ __launch_bounds__(BS) void k_num_slab_grank(const SlabRec* __restrict
     build_segids<BS, RK>(seg16, tmp);
     phase_mark(tmark, 16);
     // 1. products into registers, their 32-row blocks marked in level 1
-    // (exact integers as int: fewer VGPRs, more blocks per CU)
     int xr[RK];
     typename std::conditional<IA, int, double>::type xv[RK];
-    {
-      int sg[RK];
+    gather_products<SR, VA, IA, BS, RK>(total, seg16, srec, irA, valA, lo, xr, xv);
 #pragma unroll
-      for (int k = 0; k < RK; ++k) {
-        const int u = tid + k * BS;
-        sg[k] = u < total ? seg16[u] : -1;
-      }
-#pragma unroll
-      for (int k = 0; k < RK; ++k) {
-        xr[k] = -1;
-        if (sg[k] >= 0) {
-          const SegRec r = srec[sg[k]];
-          const RowVal x = a_rowval<SR, VA>(irA, valA, r.off + tid + k * BS, r.b, lo);
-          xr[k] = x.row;
-          if constexpr (IA) xv[k] = (int)x.v;
-          else xv[k] = x.v;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RK; ++k)
-        if (xr[k] >= 0) atomicOr(&l1[xr[k] >> 10], 1u << ((xr[k] >> 5) & 31));
-    }
-    if (has_next) fetch1(nrec);
+    for (int k = 0; k < RK; ++k)
+      if (xr[k] >= 0) atomicOr(&l1[xr[k] >> 10], 1u << ((xr[k] >> 5) & 31));
+    if (has_next) pf.fetch1(nrec, irB, valB);
     __syncthreads();
     phase_mark(tmark, 17);
     // 2. level-1 slots; vals (aliasing the staging, idle now) set to the identity
-    if (IA) {
-      const int id = SemI<SR>::identity();
-      int4* v4 = reinterpret_cast<int4*>(vals);
-      for (int j = tid; j < (nout + 3) >> 2; j += BS) v4[j] = make_int4(id, id, id, id);
-    } else {
-      const double id = Sem<SR>::identity();
-      double2* v2 = reinterpret_cast<double2*>(vals);
-      for (int j = tid; j < (nout + 1) >> 1; j += BS) v2[j] = make_double2(id, id);
-    }
+    slab_fill_identity<SR, IA, BS>(vals, nout);
     const int nslot = bitmap_group_ranks<BS, G1PT>(l1q, ng1, g1pre, tmp);
     __syncthreads();
     int sl[RK];
@@ -3132,17 +3073,12 @@ __global__ __launch_bounds__(BS) void k_num_slab_grank(const SlabRec* __restrict
           rows[rk] = lo + xr[k];
         }
     }
-    if (has_next) fetch2(nrec);
+    if (has_next) pf.fetch2(nrec, pm, last_panel(nrec));
     __syncthreads();
     phase_mark(tmark, 19);
-    // 4. rows and values in rank order: coalesced copies
-    {
-      const int* rows = reinterpret_cast<const int*>(smem + (L::ROWS_IN_L1 ? L::L1_OFF : L::ROWS_OFF));
-      for (int j = tid; j < nout; j += BS) {
-        st_rows<IA>(&out_ir[obase + j], rows[j]);
-        st_emit(&out_val[obase + j], IA ? (double)reinterpret_cast<const int*>(vals)[j] : vals[j]);
-      }
-    }
+    // 4. C's rows and values
+    slab_emit_ranked<IA, BS>(reinterpret_cast<const int*>(smem + (L::ROWS_IN_L1 ? L::L1_OFF : L::ROWS_OFF)), vals, nout,
+                             obase, out_ir, out_val);
     if ((c_dbg & 32) && tid == 0) {
       atomicAdd(&g_stat[10], (unsigned long long)total);
       atomicAdd(&g_stat[11], (unsigned long long)nout);
@@ -3428,19 +3364,33 @@ struct BigPlan {
 };
 
 
+// f(valA): A's records as the slab kernels read them (the kernels' VA is what valA points
+// to).  A's exact f32 values come as (row, f32) records whenever they exist; f64 values as
+// (row, f64) records when they were worth packing, see k_pack_rvd
+template <class F>
+static void with_a_values(const BigPlan& bp, const cbg_tile& A, F&& f) {
+  if (bp.valAp) f(bp.valAp);
+  else if (bp.valAd) f(bp.valAd);
+  else f(A.val);
+}
+// f(valA, ia): the same with the IACC tag first (decltype(ia)::value is the kernels' IA;
+// IACC only with the packed records: integers of magnitude <= 2^24 are f32-exact)
+template <class F>
+static void with_a_records(const BigPlan& bp, const cbg_tile& A, F&& f) {
+  if (bp.iacc) f(bp.valAp, std::true_type{});
+  else with_a_values(bp, A, [&](const auto* valA) { f(valA, std::false_type{}); });
+}
+template <class P>
+using records_of = std::remove_const_t<std::remove_pointer_t<P>>;
+
 template <int SR, int T, int BS>
 static void launch_slab_hash(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                              const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  auto go = [&](auto k, const auto* valA) {
-    launch_queued(k, BS, SlabHashLds<T, BS>::BYTES, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
-                  C.val, (const int4*)nullptr);
-  };
-  // (A's exact f32 values come as (row, f32) records whenever they exist; f64
-  // values as (row, f64) records when they were worth packing, see k_pack_rvd)
-  if (bp.valAp) go(k_num_slab_hash<SR, T, BS, false, PackedRV>, bp.valAp);
-  else if (bp.valAd) go(k_num_slab_hash<SR, T, BS, false, PackedRVD>, bp.valAd);
-  else go(k_num_slab_hash<SR, T, BS, false, double>, A.val);
+  with_a_values(bp, A, [&](const auto* valA) {
+    launch_queued(k_num_slab_hash<SR, T, BS, false, records_of<decltype(valA)>>, BS, SlabHashLds<T, BS>::BYTES, list, n,
+                  s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val, (const int4*)nullptr);
+  });
 }
 
 // CAP_IA: the class's cap under IACC (6 B of LDS per nonzero, SlabLds); PER_CU:
@@ -3456,15 +3406,12 @@ static void launch_slab_bitmap(const SlabRec* list, int n, const BigPlan& bp, co
     launch_queued(k, BS, lds, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val, bp.gbm.p,
                   bp.cuts.p, bp.runs.p, bp.R);
   };
-  auto go = [&](auto k, const auto* valA) { go_lds(k, SlabLds<CAP, BS>::BYTES, valA); };
-  // (IACC only with the packed records: integers of magnitude <= 2^24 are f32-exact)
   auto pick = [&](auto kept, auto staged) {
-    constexpr bool KEPT = decltype(kept)::value, RUNS = decltype(staged)::value;
-    if (bp.iacc)
-      go_lds(k_num_slab<SR, CAP_IA, BS, PackedRV, KEPT, true, RUNS>, SlabLds<CAP_IA, BS, true>::BYTES, bp.valAp);
-    else if (bp.valAp) go(k_num_slab<SR, CAP, BS, PackedRV, KEPT, false, RUNS>, bp.valAp);
-    else if (bp.valAd) go(k_num_slab<SR, CAP, BS, PackedRVD, KEPT, false, RUNS>, bp.valAd);
-    else go(k_num_slab<SR, CAP, BS, double, KEPT, false, RUNS>, A.val);
+    with_a_records(bp, A, [&](const auto* valA, auto ia) {
+      constexpr bool KEPT = decltype(kept)::value, RUNS = decltype(staged)::value, IA = decltype(ia)::value;
+      constexpr int NZ = IA ? CAP_IA : CAP;
+      go_lds(k_num_slab<SR, NZ, BS, records_of<decltype(valA)>, KEPT, IA, RUNS>, SlabLds<NZ, BS, IA>::BYTES, valA);
+    });
   };
   // (the symbolic wrote the staged runs of every bitmap-mode pair, or none)
   if (bp.all_kept && bp.runs.p) pick(std::true_type{}, std::true_type{});
@@ -3477,14 +3424,12 @@ template <int SR, int NCAP>
 static void launch_slab_rank(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                              const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  const int L = bp.iacc ? SlabRankLds<NCAP, RANK_BS, 4>::BYTES : SlabRankLds<NCAP, RANK_BS, 8>::BYTES;
-  auto go = [&](auto k, const auto* valA) {
-    launch_queued(k, RANK_BS, L, list, n, s, df, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val);
-  };
-  if (bp.iacc) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRV, true>, bp.valAp);
-  else if (bp.valAp) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRV, false>, bp.valAp);
-  else if (bp.valAd) go(k_num_slab_rank<SR, NCAP, RANK_BS, PackedRVD, false>, bp.valAd);
-  else go(k_num_slab_rank<SR, NCAP, RANK_BS, double, false>, A.val);
+  with_a_records(bp, A, [&](const auto* valA, auto ia) {
+    constexpr bool IA = decltype(ia)::value;
+    launch_queued(k_num_slab_rank<SR, NCAP, RANK_BS, records_of<decltype(valA)>, IA>, RANK_BS,
+                  SlabRankLds<NCAP, RANK_BS, IA ? 4 : 8>::BYTES, list, n, s, df, B.ir, B.val, bp.pm(), A.ir, valA, C.ir,
+                  C.val);
+  });
 }
 
 // hash-mode single-panel slabs of more than this many nonzeros run as rank
@@ -3497,15 +3442,12 @@ template <int SR, int NCAP, int SPANLOG = GRANK_SPAN_LOG, int PMAX = GRANK_PMAX>
 static void launch_slab_grank(const SlabRec* list, int n, const BigPlan& bp, const cbg_tile& A,
                               const cbg_tile& B, cbg_tile& C, hipStream_t s, DeferredFree& df) {
   if (n <= 0) return;
-  const int L = bp.iacc ? SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 4>::BYTES
-                        : SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, 8>::BYTES;
-  auto go = [&](auto k, const auto* valA) {
-    launch_queued(k, RANK_BS, L, list, n, s, df, bp.plog, B.ir, B.val, bp.pm(), A.ir, valA, C.ir, C.val);
-  };
-  if (bp.iacc) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRV, true>, bp.valAp);
-  else if (bp.valAp) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRV, false>, bp.valAp);
-  else if (bp.valAd) go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, PackedRVD, false>, bp.valAd);
-  else go(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, double, false>, A.val);
+  with_a_records(bp, A, [&](const auto* valA, auto ia) {
+    constexpr bool IA = decltype(ia)::value;
+    launch_queued(k_num_slab_grank<SR, NCAP, RANK_BS, SPANLOG, PMAX, records_of<decltype(valA)>, IA>, RANK_BS,
+                  SlabGRankLds<NCAP, RANK_BS, SPANLOG, PMAX, IA ? 4 : 8>::BYTES, list, n, s, df, bp.plog, B.ir, B.val,
+                  bp.pm(), A.ir, valA, C.ir, C.val);
+  });
 }
 
 // ncls[c] slabs of class c, stored consecutively in `list` (k_slab_fill)
