@@ -91,6 +91,7 @@ EXPORTS = [
     "cbg_tile_spref", "cbg_grid_spref", "cbg_rand_perm", "cbg_spref_sort_bounds", "cbg_last_spref_stats",
     "cbg_grid_hipmcl_prepared", "cbg_grid_nonisolated",
     "cbg_tile_ewise", "cbg_ewise_bounds", "cbg_last_ewise_stats", "cbg_grid_betwcent", "cbg_last_betwcent_stats",
+    "cbg_tile_spmspv_max", "cbg_tile_pull_max", "cbg_bfs_bounds", "cbg_grid_bfs", "cbg_last_bfs_stats",
 ]
 RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT = 0, 1, 2, 3  # cbg_grid_reduce_cols
 _REDS = {"sum": RED_SUM, "plus": RED_SUM, "max": RED_MAX, "maximum": RED_MAX, "sumsq": RED_SUMSQ, "count": RED_COUNT}
@@ -119,6 +120,19 @@ class CBetwcentParams(ctypes.Structure):
 
 # void (*cbg_betwcent_level_fn)(void* user, int64 batch, int64 level, int64 fringe_nnz)
 BETWCENT_LEVEL_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64)
+BFS_AUTO, BFS_TOPDOWN, BFS_BOTTOMUP = 0, 1, 2
+_BFS_DIR = {"auto": BFS_AUTO, "topdown": BFS_TOPDOWN, "top-down": BFS_TOPDOWN, "push": BFS_TOPDOWN,
+            "bottomup": BFS_BOTTOMUP, "bottom-up": BFS_BOTTOMUP, "pull": BFS_BOTTOMUP}
+
+
+class CBfsParams(ctypes.Structure):
+    """cbg_bfs_params: direction, the two cut-offs (< 0: the reference's rule), the local transpose or NULL"""
+    _fields_ = [("direction", ctypes.c_int32), ("up_cutoff", ctypes.c_int64), ("down_cutoff", ctypes.c_int64),
+                ("At_local", ctypes.POINTER(CTile))]
+
+
+# void (*cbg_bfs_level_fn)(void* user, int64 level, int direction, int64 frontier, int64 pred)
+BFS_LEVEL_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64)
 PERM_SEED = 0x5EED  # HipMCL(randpermute=True) default
 # void (*cbg_hipmcl_iter_fn)(void* user, int64 iter, double chaos, int64 nnz, double ms_expand, ms_prune, ms_inflate)
 HIPMCL_ITER_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.c_double,
@@ -230,6 +244,11 @@ def lib():
         "cbg_tile_ewise": ([T, T, i32, T], i32),
         "cbg_ewise_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_ewise_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_tile_spmspv_max": ([T, vp, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
+        "cbg_tile_pull_max": ([T, vp, i64, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "cbg_bfs_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_grid_bfs": ([vp, T, i64, i64, ctypes.POINTER(CBfsParams), BFS_LEVEL_FN, vp, vp, vp], i32),
+        "cbg_last_bfs_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_spref_sort_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_spref_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_grid_nonisolated": ([vp, T, i64, vp, ctypes.POINTER(i64)], i32),
@@ -391,6 +410,24 @@ class Tile:
         _check(lib().cbg_tile_ewise(ctypes.byref(self.c), ctypes.byref(other.c) if other is not None else None,
                                     int(code), ctypes.byref(t.c)))
         return t
+
+    def pull_max(self, xind, skip=None):
+        """self is At = A.transpose(): A's SelectMax product with the sparse vector whose entries are xind
+        (ascending local columns of A, the value of an entry its id), by pulling (cbg_tile_pull_max).
+        skip: per row of A, nonzero leaves the row out.  -> (yind, yval, entries_read)"""
+        x, nx = _index_arg(np.asarray(xind, np.int64))
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.uint8)
+            if len(sk) != self.n:
+                raise CbgError(INVALIDPARAMS, "pull_max: skip has one byte per row of A")
+            if len(sk) == 0:
+                sk = None
+        yi, yv = np.zeros(max(self.n, 1), np.int64), np.zeros(max(self.n, 1), np.int64)
+        ny, er = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().cbg_tile_pull_max(ctypes.byref(self.c), x.ctypes.data, nx, sk.ctypes.data if sk is not None else None,
+                                       yi.ctypes.data, yv.ctypes.data, ctypes.byref(ny), ctypes.byref(er)))
+        return yi[:ny.value].copy(), yv[:ny.value].copy(), int(er.value)
 
     def split_cols(self, cut):
         """SpDCCols::Split (SpDCCols.cpp:905-930)"""
@@ -1512,6 +1549,77 @@ def betwcent_stats():
     lib().cbg_last_betwcent_stats(c, 4, ms)
     return dict(batches=int(c[0]), levels=int(c[1]), deepest=int(c[2]), fringe_entries=int(c[3]), ms_forward=ms[0],
                 ms_ewise=ms[1], ms_backward=ms[2], ms_dense=ms[3], ms_total=ms[4])
+
+
+def SpMSpV(tile, xind, xval=None):
+    """SpMV<SelectMaxSRing<bool,int64>> of a device tile with a sparse vector (SpImpl.cpp:168-221,
+    cbg_tile_spmspv_max): xind ascending distinct local columns, xval their int64 values (None: the
+    ids, the reference's indexisvalue).  y[i] = max over the stored tile(i, j), j in xind, of x[j];
+    stored values are not read.  -> (yind ascending, yval)"""
+    x, nx = _index_arg(np.asarray(xind, np.int64))
+    v = None
+    if xval is not None:
+        v, nv = _index_arg(np.asarray(xval, np.int64))
+        if nv != nx:
+            raise CbgError(INVALIDPARAMS, "SpMSpV: xval has one value per index")
+    yi, yv = np.zeros(max(tile.m, 1), np.int64), np.zeros(max(tile.m, 1), np.int64)
+    ny = ctypes.c_int64()
+    _check(lib().cbg_tile_spmspv_max(ctypes.byref(tile.c), x.ctypes.data, v.ctypes.data if v is not None else None, nx,
+                                     yi.ctypes.data, yv.ctypes.data, ctypes.byref(ny)))
+    return yi[:ny.value].copy(), yv[:ny.value].copy()
+
+
+def bfs_bounds():
+    """[C, S] (cbg_bfs_bounds): the entries of a frontier column one push unit takes, and the longest
+    row the pull scans with one lane (longer rows take a wave)"""
+    b = (ctypes.c_int64 * 2)()
+    n = lib().cbg_bfs_bounds(b, 2)
+    return [int(x) for x in b[:n]]
+
+
+def BFS(A, root, direction="auto", on_level=None, At=None, up_cutoff=None, down_cutoff=None):
+    """Single-source breadth-first search (TopDownBFS.cpp:427-443, DirOptBFS.cpp:360-445) of the graph
+    whose edges j -> i are A's stored entries A(i, j) -- the reference's y = A x, the transpose of
+    BetwCent's orientation; values are ignored.  -> (parents, levels), gn int64 each, the same on
+    every rank: parents[root] = root, parents[v] = the largest u of the level before with A(v, u)
+    stored, -1 where unreached.  direction "auto" (the reference's rule), "topdown" or "bottomup".
+    At: the Tile A.tile.transpose() (None: made at the first pull step).  up_cutoff / down_cutoff:
+    None for the reference's figures.  on_level(level, direction, frontier, pred) runs before every
+    step, direction "d" (push) or "u" (pull); an exception it raises is raised again after the
+    collective has finished.  Collective."""
+    if A.gm != A.gn:
+        raise CbgError(DIMMISMATCH, "BFS needs a square matrix")
+    d = _BFS_DIR.get(direction, direction) if isinstance(direction, str) else direction
+    if d not in (BFS_AUTO, BFS_TOPDOWN, BFS_BOTTOMUP):
+        raise CbgError(INVALIDPARAMS, f"BFS: unknown direction {direction!r} (auto, topdown, bottomup)")
+    at = At.tile if isinstance(At, SpParMat) else At
+    prm = CBfsParams(int(d), -1 if up_cutoff is None else int(up_cutoff), -1 if down_cutoff is None else int(down_cutoff),
+                     ctypes.pointer(at.c) if at is not None else None)
+    parents, levels = np.zeros(max(A.gn, 1), np.int64), np.zeros(max(A.gn, 1), np.int64)
+    errors = []
+
+    def _cb(user, level, dr, frontier, pred):
+        try:
+            on_level(int(level), "u" if dr == BFS_BOTTOMUP else "d", int(frontier), int(pred))
+        except Exception as e:  # noqa: BLE001 -- reported after the collective finishes
+            errors.append(e)
+
+    cb = BFS_LEVEL_FN(_cb) if on_level is not None else BFS_LEVEL_FN()
+    _check(lib().cbg_grid_bfs(A.grid.h, ctypes.byref(A.tile.c), A.gn, int(root), ctypes.byref(prm), cb, None,
+                              parents.ctypes.data, levels.ctypes.data))
+    if errors:
+        raise errors[0]
+    return parents[:A.gn], levels[:A.gn]
+
+
+def bfs_stats():
+    """the last BFS on this rank (cbg_last_bfs_stats): levels is the tree's depth (steps run: levels + 1);
+    the times are host ms"""
+    c, ms = (ctypes.c_int64 * 8)(), (ctypes.c_double * 5)()
+    lib().cbg_last_bfs_stats(c, 8, ms)
+    return dict(levels=int(c[0]), reached=int(c[1]), edges=int(c[2]), push_steps=int(c[3]), pull_steps=int(c[4]),
+                push_units=int(c[5]), pull_rows=int(c[6]), pull_entries=int(c[7]), ms_push=ms[0], ms_pull=ms[1],
+                ms_update=ms[2], ms_comm=ms[3], ms_total=ms[4])
 
 
 def RemoveIsolated(A):

@@ -47,6 +47,8 @@ int grid_spref(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const int
                const int64_t* ci, int64_t nci, cbg_tile& out);
 int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn, const int64_t* roots, int64_t nroots,
                   const cbg_betwcent_params& P, cbg_betwcent_level_fn fn, void* user, double* bc);
+int grid_bfs(cbg_grid* g, const cbg_tile& A, int64_t gn, int64_t root, const cbg_bfs_params& P, cbg_bfs_level_fn fn,
+             void* user, int64_t* parents, int64_t* levels);
 void rand_perm(int64_t n, uint64_t seed, int64_t* p);
 int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids);
 int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
@@ -931,6 +933,63 @@ int cbg_last_betwcent_stats(int64_t* counts, int n, double* ms) {
   for (int i = 0; counts && i < n && i < CBG_BC_N; ++i) counts[i] = b.counts[i];
   for (int i = 0; ms && i < CBG_BC_MS_N; ++i) ms[i] = b.ms[i];
   return CBG_BC_N;
+}
+
+// ---------------- single-source breadth-first search ----------------
+// ascending, distinct, inside [0, n)
+static bool bfs_index_ok(const int64_t* x, int64_t nx, int64_t n) {
+  if (nx < 0 || (nx > 0 && !x)) return false;
+  for (int64_t k = 0; k < nx; ++k)
+    if (x[k] < 0 || x[k] >= n || (k > 0 && x[k] <= x[k - 1])) return false;
+  return true;
+}
+
+int cbg_tile_spmspv_max(const cbg_tile* A, const int64_t* xind, const int64_t* xval, int64_t nx, int64_t* yind,
+                        int64_t* yval, int64_t* ny) {
+  if (int rc = check_tile(A, true, "A")) return rc;
+  if (!ny || (A->m > 0 && (!yind || !yval))) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_spmspv_max: an output is NULL");
+  if (!bfs_index_ok(xind, nx, A->n))
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_spmspv_max: xind holds nx >= 0 distinct ascending columns below A->n");
+  return guard([&] {
+    cbg::bfs_stats() = cbg::BfsStats{};
+    cbg::bfs_spmspv_max(*A, xind, xval, nx, yind, yval, ny, default_stream());
+    return CBG_OK;
+  });
+}
+
+int cbg_tile_pull_max(const cbg_tile* At, const int64_t* xind, int64_t nx, const uint8_t* skip, int64_t* yind,
+                      int64_t* yval, int64_t* ny, int64_t* entries_read) {
+  if (int rc = check_tile(At, true, "At")) return rc;
+  if (!ny || (At->n > 0 && (!yind || !yval))) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_pull_max: an output is NULL");
+  if (!bfs_index_ok(xind, nx, At->m))
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_pull_max: xind holds nx >= 0 distinct ascending columns below At->m");
+  return guard([&] {
+    cbg::bfs_stats() = cbg::BfsStats{};
+    cbg::bfs_pull_max(*At, xind, nx, skip, yind, yval, ny, entries_read, default_stream());
+    return CBG_OK;
+  });
+}
+
+int cbg_bfs_bounds(int64_t* bounds, int n) { return cbg::bfs_bounds(bounds, n); }
+
+int cbg_grid_bfs(cbg_grid* g, const cbg_tile* A_local, int64_t gn, int64_t root, const cbg_bfs_params* p,
+                 cbg_bfs_level_fn fn, void* user, int64_t* parents, int64_t* levels) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(A_local, true, "A");
+  if (!arg && p && p->At_local) arg = check_tile(p->At_local, true, "At");
+  if (!arg && (!p || !parents)) arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_bfs: params and parents are needed");
+  if (!arg && (p->direction < CBG_BFS_AUTO || p->direction > CBG_BFS_BOTTOMUP))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_bfs: direction is CBG_BFS_AUTO, _TOPDOWN or _BOTTOMUP");
+  if (!arg && (root < 0 || root >= gn)) arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_bfs: the root is a vertex below gn");
+  // every check above precedes any device work; the code is agreed over the grid
+  return grid_call(g, arg, [&] { return cbg::grid_bfs(g, *A_local, gn, root, *p, fn, user, parents, levels); });
+}
+
+int cbg_last_bfs_stats(int64_t* counts, int n, double* ms) {
+  const cbg::BfsStats& b = cbg::bfs_stats();
+  for (int i = 0; counts && i < n && i < CBG_BFS_N; ++i) counts[i] = b.counts[i];
+  for (int i = 0; ms && i < CBG_BFS_MS_N; ++i) ms[i] = b.ms[i];
+  return CBG_BFS_N;
 }
 
 int cbg_rand_perm(int64_t n, uint64_t seed, int64_t* p) {

@@ -467,6 +467,36 @@ struct BetwcentStats {
 };
 BetwcentStats& betwcent_stats();
 
+// SelectMax matrix x sparse vector and the breadth-first search's vector steps (cbg_bfs.hip)
+struct BfsStats {
+  int64_t counts[CBG_BFS_N] = {};
+  double ms[CBG_BFS_MS_N] = {};
+};
+BfsStats& bfs_stats();  // the calling thread's; reset by the C ABI's entry points
+int bfs_bounds(int64_t* bounds, int n);
+void bfs_spmspv_max(const cbg_tile& A, const int64_t* xind, const int64_t* xval, int64_t nx, int64_t* yind,
+                    int64_t* yval, int64_t* ny, hipStream_t s);
+void bfs_pull_max(const cbg_tile& At, const int64_t* xind, int64_t nx, const uint8_t* skip, int64_t* yind,
+                  int64_t* yval, int64_t* ny, int64_t* entries_read, hipStream_t s);
+// push: pos = A's column map; fl[nf] the frontier's local columns, ustart the scan of their units; cand: -1 = none
+void bfs_push_device(const cbg_tile& A, const int32_t* pos, const int32_t* fl, int64_t nf, const int64_t* ustart,
+                     int64_t units, int32_t* cand, hipStream_t s);
+// pull: bits = the frontier over the global columns, coff = At's row offset in them; parent / skip may be
+// NULL; longq: At.nzc slots; stat (3 words, zeroed by the caller): rows scanned, entries read, rows queued
+void bfs_pull_device(const cbg_tile& At, const u64* bits, int64_t coff, const int64_t* parent, const uint8_t* skip,
+                     int32_t* cand, int32_t* longq, u64* stat, hipStream_t s);
+void bfs_cand_global(const int32_t* cand, int64_t lm, int64_t coff, int64_t* candg, hipStream_t s);
+void bfs_cand_max(int64_t* candg, const int64_t* all, int P, int64_t lm, hipStream_t s);  // all: P blocks of lm
+// rowbits: wb words of the row block's new frontier (rewritten); *count += their number
+void bfs_update(int64_t lm, const int64_t* candg, int64_t* parent, int64_t* level, int64_t lev, u64* rowbits, int64_t wb,
+                u64* count, hipStream_t s);
+// all: pr blocks of wb words, block q the rows from q * per -> bits over gn vertices
+void bfs_assemble_bits(const u64* all, int pr, int64_t per, int64_t wb, int64_t gn, u64* bits, hipStream_t s);
+// the set bits of [coff, coff + ln) -> fl (ascending local ids), nu (their units); stat (3 words, zeroed
+// here): the list's length, pred, units; scratch: 2 * (ceil(ln / 64) + 1) int64; fl / nu: room for ln
+void bfs_compact(const u64* bits, int64_t coff, int64_t ln, const int64_t* len, int32_t* fl, int64_t* nu,
+                 int64_t* scratch, u64* stat, hipStream_t s, DeferredFree& df);
+
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);
 void store_probe(int64_t bytes, int width);

@@ -2250,6 +2250,218 @@ int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn
   return CBG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Single-source breadth-first search (include/cbg.h): the loop of TopDownBFS.cpp:427-443 with the
+// direction rule of DirOptBFS.cpp:364-365, 388, 409.  The vector steps are in cbg_bfs.hip.
+// State on the device: parents and levels of this rank's row block (equal on the ranks of a grid row),
+// the frontier as a bitmap over all gn vertices (equal on every rank), and this rank's column block of
+// it as a list.  Every step ends in one agreement that also sums the frontier and its pred.
+// ---------------------------------------------------------------------------
+int grid_bfs(cbg_grid* g, const cbg_tile& A, int64_t gn, int64_t root, const cbg_bfs_params& P, cbg_bfs_level_fn fn,
+             void* user, int64_t* parents, int64_t* levels) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  check_usable(g);
+  BfsStats& st = bfs_stats();
+  st = BfsStats{};
+  const auto t_all = clk::now();
+  hipStream_t cs = g->compute;
+  int64_t roff = 0, coff = 0, toff = 0, tcoff = 0;
+  int rc = !tile_place(g, A, gn, gn, &roff, &coff) ||
+                   (P.At_local && (P.At_local->m != A.n || P.At_local->n != A.m || !P.At_local->on_device))
+               ? (int)CBG_ERR_DIMMISMATCH
+               : (int)CBG_OK;
+  if ((rc = agree(g, rc))) return rc;
+  const int64_t lm = A.m, ln = A.n, per = gn / g->pr;
+  const int64_t lmax = gn - (int64_t)(g->pr - 1) * per;  // the last row block is the longest
+  const int64_t wb = (lmax + 63) / 64, wg = (gn + 63) / 64, nw = (ln + 63) / 64;
+  // stored entries over the grid: the cut-offs
+  int64_t nnz = A.nnz;
+  if ((rc = agree(g, step([&] { allreduce_sum_i64(g, &nnz); })))) return rc;
+  const int64_t up = P.up_cutoff >= 0 ? P.up_cutoff : nnz / 20;
+  const int64_t down = P.down_cutoff >= 0 ? P.down_cutoff
+                       : nnz > 0          ? (int64_t)((double)gn * (double)gn / ((double)nnz * 12.0))
+                                          : 0;
+
+  DBuf<int64_t> parent, level, candg, all_cand, len, nu, scratch;
+  DBuf<int32_t> cand, pos, fl, longq;
+  DBuf<u64> bits, rowbits, all_bits, stat;
+  TileGuard at_own;
+  const cbg_tile* At = P.At_local;
+  u64 sh[8] = {};  // stat's host copy: 0 new, 1 pull rows, 2 pull entries, 3 queued, 4 list length, 5 pred, 6 units
+  // this rank's part of the current frontier, and the sums over the grid
+  int64_t nf = 0, units = 0, frontier = 0, pred = 0;
+  // compaction of the current bits, then the agreement that sums the frontier and pred over the grid
+  auto compact_and_agree = [&](int code) {
+    int r = code ? code : step([&] {
+      DeferredFree df;
+      bfs_compact(bits.p, coff, ln, len.p, fl.p, nu.p, scratch.p, stat.p + 4, cs, df);
+      CBG_HIP(hipMemcpyAsync(sh + 4, stat.p + 4, sizeof(u64) * 3, hipMemcpyDeviceToHost, cs));
+      CBG_HIP(hipStreamSynchronize(cs));
+      nf = (int64_t)sh[4];
+      units = (int64_t)sh[6];
+      if (nf > 0) exclusive_scan_i64(nu.p, nu.p + ln + 1, nf, cs, &df);  // ustart
+      CBG_HIP(hipStreamSynchronize(cs));
+      df.synced = true;
+    });
+    int64_t v[3] = {r, r ? 0 : nf, r ? 0 : (int64_t)sh[5]};
+    std::vector<int64_t> all((size_t)3 * g->nranks);
+    const int rr = step([&] { allgather_i64(g, COMM_WORLD, v, all.data(), 3); });
+    if (rr) return rr;
+    int64_t w = 0, f = 0, pd = 0;
+    for (int q = 0; q < g->nranks; ++q) w = std::max(w, all[3 * q]), f += all[3 * q + 1], pd += all[3 * q + 2];
+    frontier = f / g->pr;  // every grid row lists the whole frontier once
+    pred = pd;
+    return (int)w;
+  };
+
+  rc = step([&] {
+    parent.reset(std::max<int64_t>(lm, 1));
+    level.reset(std::max<int64_t>(lm, 1));
+    candg.reset(std::max<int64_t>(lm, 1));
+    cand.reset(std::max<int64_t>(lm, 1));
+    if (g->pc > 1 && g->host_mode) all_cand.reset((size_t)std::max<int64_t>(lm, 1) * g->pc);
+    pos.reset(std::max<int64_t>(ln, 1));
+    len.reset(std::max<int64_t>(ln, 1));
+    fl.reset(std::max<int64_t>(ln, 1));
+    nu.reset(2 * ln + 2);
+    scratch.reset(2 * (nw + 1));
+    bits.reset(std::max<int64_t>(wg, 1));
+    rowbits.reset(std::max<int64_t>(wb, 1));
+    all_bits.reset((size_t)std::max<int64_t>(wb, 1) * g->pr);
+    stat.reset(8);
+    CBG_HIP(hipMemsetAsync(parent.p, 0xff, sizeof(int64_t) * std::max<int64_t>(lm, 1), cs));
+    CBG_HIP(hipMemsetAsync(level.p, 0xff, sizeof(int64_t) * std::max<int64_t>(lm, 1), cs));
+    CBG_HIP(hipMemsetAsync(bits.p, 0, sizeof(u64) * std::max<int64_t>(wg, 1), cs));
+    CBG_HIP(hipMemsetAsync(rowbits.p, 0, sizeof(u64) * std::max<int64_t>(wb, 1), cs));
+    tile_col_map(A, pos.p, len.p, cs);
+    const u64 one = 1ull << (root & 63);
+    const int64_t zero = 0;
+    CBG_HIP(hipMemcpyAsync(bits.p + (root >> 6), &one, sizeof(u64), hipMemcpyHostToDevice, cs));
+    if (root >= roff && root < roff + lm) {  // as DirOptBFS.cpp:371
+      CBG_HIP(hipMemcpyAsync(parent.p + (root - roff), &root, sizeof(int64_t), hipMemcpyHostToDevice, cs));
+      CBG_HIP(hipMemcpyAsync(level.p + (root - roff), &zero, sizeof(int64_t), hipMemcpyHostToDevice, cs));
+    }
+    CBG_HIP(hipStreamSynchronize(cs));
+  });
+  if ((rc = compact_and_agree(rc))) return rc;
+
+  bool pulling = P.direction == CBG_BFS_BOTTOMUP;
+  int64_t last = 0;
+  st.counts[CBG_BFS_REACHED] = 1;
+  for (int64_t lev = 1; frontier > 0; ++lev) {
+    if (P.direction == CBG_BFS_AUTO && !pulling && pred > up && last < frontier) pulling = true;
+    if (fn) fn(user, lev, pulling ? CBG_BFS_BOTTOMUP : CBG_BFS_TOPDOWN, frontier, pred);
+    st.counts[CBG_BFS_EDGES] += pred;
+    st.counts[pulling ? CBG_BFS_PULL_STEPS : CBG_BFS_PUSH_STEPS] += 1;
+    if (pulling && !At) {  // the local tile's transpose: no grid transpose, so any grid shape
+      const auto t0 = clk::now();
+      rc = step([&] {
+        tile_transpose(A, at_own.t, cs);
+        CBG_HIP(hipStreamSynchronize(cs));
+      });
+      st.ms[CBG_BFS_MS_PULL] += ms_since(t0);
+      if ((rc = agree(g, rc))) return rc;
+      At = &at_own.t;
+    }
+    // 1. push or pull into cand, as global ids
+    auto t0 = clk::now();
+    rc = step([&] {
+      CBG_HIP(hipMemsetAsync(stat.p, 0, sizeof(u64) * 4, cs));
+      CBG_HIP(hipMemsetAsync(cand.p, 0xff, sizeof(int32_t) * std::max<int64_t>(lm, 1), cs));
+      if (pulling) {
+        if (!longq.p) longq.reset(std::max<int64_t>(At->nzc, 1));
+        bfs_pull_device(*At, bits.p, coff, parent.p, nullptr, cand.p, longq.p, stat.p + 1, cs);
+      } else {
+        bfs_push_device(A, pos.p, fl.p, nf, nu.p + ln + 1, units, cand.p, cs);
+      }
+      bfs_cand_global(cand.p, lm, coff, candg.p, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    st.ms[pulling ? CBG_BFS_MS_PULL : CBG_BFS_MS_PUSH] += ms_since(t0);
+    if ((rc = agree(g, rc))) return rc;
+    // 2. the maximum over the grid row
+    t0 = clk::now();
+    rc = step([&] {
+      if (g->pc == 1 || lm == 0) return;
+      if (g->host_mode) {
+        allgather_device(g, COMM_ROW, candg.p, all_cand.p, sizeof(int64_t) * lm);
+        bfs_cand_max(candg.p, all_cand.p, g->pc, lm, cs);
+        CBG_HIP(hipStreamSynchronize(cs));
+      } else {
+        CBG_NCCL(ncclAllReduce(candg.p, candg.p, (size_t)lm, ncclInt64, ncclMax, g->row, g->comm));
+        wait_comm(g);
+      }
+    });
+    st.ms[CBG_BFS_MS_COMM] += ms_since(t0);
+    if ((rc = agree(g, rc))) return rc;
+    // 3. the update of the row block
+    t0 = clk::now();
+    rc = step([&] {
+      bfs_update(lm, candg.p, parent.p, level.p, lev, rowbits.p, wb, stat.p, cs);
+      CBG_HIP(hipMemcpyAsync(sh, stat.p, sizeof(u64) * 4, hipMemcpyDeviceToHost, cs));
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    st.ms[CBG_BFS_MS_UPDATE] += ms_since(t0);
+    if ((rc = agree(g, rc))) return rc;
+    // 4. the row blocks' bits along the grid column -> the frontier over all vertices
+    t0 = clk::now();
+    rc = step([&] {
+      if (wb == 0) return;
+      if (g->pr > 1) allgather_device(g, COMM_COL, rowbits.p, all_bits.p, sizeof(u64) * wb);
+      bfs_assemble_bits(g->pr > 1 ? all_bits.p : rowbits.p, g->pr, per, wb, gn, bits.p, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+    });
+    st.ms[CBG_BFS_MS_COMM] += ms_since(t0);
+    // 5. the new frontier's list, size and pred (the agreement of step 4 is this one)
+    if (!pulling) st.counts[CBG_BFS_PUSH_UNITS] += units;
+    else st.counts[CBG_BFS_PULL_ROWS] += (int64_t)sh[1], st.counts[CBG_BFS_PULL_ENTRIES] += (int64_t)sh[2];
+    last = frontier;
+    t0 = clk::now();
+    if ((rc = compact_and_agree(rc))) return rc;
+    st.ms[CBG_BFS_MS_UPDATE] += ms_since(t0);
+    st.counts[CBG_BFS_REACHED] += frontier;
+    if (frontier > 0) st.counts[CBG_BFS_LEVELS] = lev;
+    if (P.direction == CBG_BFS_AUTO && pulling && frontier < down && last > frontier) pulling = false;
+  }
+  // units, rows and entries over the grid
+  rc = step([&] {
+    int64_t v[3] = {st.counts[CBG_BFS_PUSH_UNITS], st.counts[CBG_BFS_PULL_ROWS], st.counts[CBG_BFS_PULL_ENTRIES]};
+    std::vector<int64_t> all((size_t)3 * g->nranks);
+    allgather_i64(g, COMM_WORLD, v, all.data(), 3);
+    for (int k = 0; k < 3; ++k) {
+      int64_t s = 0;
+      for (int q = 0; q < g->nranks; ++q) s += all[3 * q + k];
+      st.counts[CBG_BFS_PUSH_UNITS + k] = s;
+    }
+  });
+  if ((rc = agree(g, rc))) return rc;
+  // every row block to every rank
+  rc = step([&] {
+    if (g->pr == 1) {  // the one row block is the whole vector: straight into the caller's arrays
+      if (lm) CBG_HIP(hipMemcpy(parents, parent.p, sizeof(int64_t) * lm, hipMemcpyDeviceToHost));
+      if (lm && levels) CBG_HIP(hipMemcpy(levels, level.p, sizeof(int64_t) * lm, hipMemcpyDeviceToHost));
+      return;
+    }
+    const int64_t l1 = std::max<int64_t>(lmax, 1);
+    std::vector<int64_t> mine((size_t)2 * l1, -1), col((size_t)2 * l1 * g->pr);
+    if (lm) CBG_HIP(hipMemcpy(mine.data(), parent.p, sizeof(int64_t) * lm, hipMemcpyDeviceToHost));
+    if (lm) CBG_HIP(hipMemcpy(mine.data() + l1, level.p, sizeof(int64_t) * lm, hipMemcpyDeviceToHost));
+    allgather_bytes(g, COMM_COL, mine.data(), col.data(), sizeof(int64_t) * 2 * l1);
+    for (int q = 0; q < g->pr; ++q) {
+      int64_t a = 0, b = 0;
+      block_span(gn, g->pr, q, a, b);
+      for (int64_t i = a; i < b; ++i) {
+        parents[i] = col[(size_t)q * 2 * l1 + (i - a)];
+        if (levels) levels[i] = col[(size_t)q * 2 * l1 + l1 + (i - a)];
+      }
+    }
+  });
+  if ((rc = agree(g, rc))) return rc;
+  st.ms[CBG_BFS_MS_TOTAL] = ms_since(t_all);
+  return CBG_OK;
+}
+
 }  // namespace cbg
 
 extern "C" int cbg_get_unique_id(void* id) {

@@ -969,6 +969,35 @@ std::vector<double> BetwCent(SpParMat<IT, NT, DER>& A, const std::vector<IT>& ro
   return bc;
 }
 
+// Single-source breadth-first search (Applications/TopDownBFS.cpp:427-443, DirOptBFS.cpp:360-445,
+// cbg_grid_bfs).  ORIENTATION: the reference's y = A x, so A(i, j) stored = an edge j -> i -- the
+// transpose of BetwCent's A; values ignored.  parents[root] = root, parents[v] = the largest u of the
+// level before with A(v, u) stored, -1 / level -1 where unreached; the same on every rank.
+// direction: CBG_BFS_AUTO (the reference's rule), _TOPDOWN or _BOTTOMUP.  At: the local tile's
+// transpose (cbg_tile_transpose), or NULL: made at the first pull step.  trace: 'd' (push) or 'u'
+// (pull) per step.
+struct BFSResult {
+  std::vector<int64_t> parents, levels;
+  std::string trace;
+};
+template <typename IT, typename NT, typename DER>
+BFSResult BFS(SpParMat<IT, NT, DER>& A, IT root, int direction = CBG_BFS_AUTO, const cbg_tile* At = nullptr,
+              int64_t up_cutoff = -1, int64_t down_cutoff = -1) {
+  const cbg_bfs_params p = {direction, up_cutoff, down_cutoff, At};
+  BFSResult r;
+  r.parents.resize((size_t)std::max<int64_t>(A.getncol(), 1));
+  r.levels.resize(r.parents.size());
+  auto fn = [](void* user, int64_t, int dir, int64_t, int64_t) {
+    static_cast<std::string*>(user)->push_back(dir == CBG_BFS_BOTTOMUP ? 'u' : 'd');
+  };
+  cbg_abort_on(cbg_grid_bfs(A.commGrid->handle(), A.spSeq->tile(), A.getncol(), (int64_t)root, &p, fn, &r.trace,
+                            r.parents.data(), r.levels.data()),
+               "BFS");
+  r.parents.resize((size_t)A.getncol());
+  r.levels.resize((size_t)A.getncol());
+  return r;
+}
+
 // BlockSpGEMM (BlockSpGEMM.h:14-131): C = A*B block by block, A split into br
 // row blocks and B into bc column blocks (bi = 1), each block product a
 // Mult_AnXBn_DoubleBuff

@@ -628,6 +628,69 @@ enum { CBG_BC_MS_FORWARD = 0, CBG_BC_MS_EWISE = 1, CBG_BC_MS_BACKWARD = 2, CBG_B
        CBG_BC_MS_N = 5 };
 int cbg_last_betwcent_stats(int64_t* counts, int n, double* ms);
 
+/* ---------------- single-source breadth-first search ----------------
+ * Applications/TopDownBFS.cpp:427-443 and DirOptBFS.cpp:360-445: the parent tree of a search from one root
+ * with SpMV<SelectMaxSRing<bool,int64>> (Semirings.h:190-210), pushing (top-down) or pulling (bottom-up).
+ *
+ * ORIENTATION: the reference's y = A x.  A stored A(i, j) is the edge j -> i, and column j lists what j
+ * reaches.  This is the TRANSPOSE of what cbg_grid_betwcent calls A (there a stored A(i, j) is i -> j).
+ * Stored values are ignored: every stored entry, an explicit zero included, is `true`.
+ *
+ * SpMXSpV with SelectMaxSRing<bool,int64> (SpImpl.cpp:168-221) on one device tile: xind HOST, nx distinct
+ * local column ids, ascending; xval HOST or NULL (NULL: indexisvalue, the value is the id).  yind / yval: HOST,
+ * room for A->m; *ny entries, yind ascending.  y[i] = max over stored A(i, j), j in xind, of x[j].
+ * An unsorted, repeated or outside xind, a negative count or a NULL output: CBG_ERR_INVALIDPARAMS before any
+ * device work. */
+int cbg_tile_spmspv_max(const cbg_tile* A, const int64_t* xind, const int64_t* xval, int64_t nx,
+                        int64_t* yind, int64_t* yval, int64_t* ny);
+/* the same product with xval == NULL, by pulling: At = cbg_tile_transpose(A); skip (HOST, At->n bytes, may be
+ * NULL): rows with skip[i] != 0 are left out of y.  *entries_read (may be NULL): entries a serial descending scan
+ * reads, the hit included (a row without a hit: its length). */
+int cbg_tile_pull_max(const cbg_tile* At, const int64_t* xind, int64_t nx, const uint8_t* skip,
+                      int64_t* yind, int64_t* yval, int64_t* ny, int64_t* entries_read);
+/* bounds[0] = C, the entries of a frontier column one push unit takes; bounds[1] = the longest row the pull
+ * scans with one lane (longer rows take a wave each, 64 entries per step from the end).
+ * bounds[i] for i < min(n, 2); returns 2 */
+int cbg_bfs_bounds(int64_t* bounds, int n);
+
+/* The search, collective over any pr x pc grid.  A_local: this rank's tile of the gn x gn matrix.
+ * parents / levels (levels may be NULL): HOST, gn int64, the same on every rank: parents[root] = root (as
+ * DirOptBFS.cpp:371), parents[v] = the largest u of the level before with A(v, u) stored, -1 where the root
+ * does not reach; levels[root] = 0, -1 where unreached.  max is exact and order-free: the same bits in
+ * either direction, on every grid and transport.
+ * Per step: push the frontier's columns of the local tile (atomic max per entry) or pull over the local
+ * transpose (every parentless row scans its columns downward and stops at the first one in the frontier) into
+ * a dense candidate array; maximum of the candidates, as global ids, over the grid row; new = candidate and no
+ * parent yet; the new frontier's bits allgathered along the grid column.
+ * direction CBG_BFS_AUTO, the reference's rule with nnz the stored entries over the grid: start pushing;
+ * before a step, if pushing and pred > up_cutoff and the frontier grew, pull; after a pull step, if the new
+ * frontier is smaller than down_cutoff and shrank, push.  pred = the summed column lengths of the frontier.
+ * up_cutoff / down_cutoff < 0: nnz / 20 and (int64)(double(gn) * gn / (nnz * 12.0)) (0 when nnz = 0).
+ * fn (may be NULL): called on every rank before every step with the step (from 1), the direction taken
+ * (CBG_BFS_TOPDOWN or _BOTTOMUP), the frontier's size and its pred.  The last step finds nothing.
+ * root outside [0, gn), a bad direction or a NULL parents: CBG_ERR_INVALIDPARAMS; a tile that is not this
+ * rank's block of gn x gn (or an At_local that is not its transpose's shape): CBG_ERR_DIMMISMATCH; on every
+ * rank before any device work. */
+enum { CBG_BFS_AUTO = 0, CBG_BFS_TOPDOWN = 1, CBG_BFS_BOTTOMUP = 2 };
+typedef struct cbg_bfs_params {
+  int32_t direction;
+  int64_t up_cutoff, down_cutoff; /* < 0: the reference's rule */
+  const cbg_tile* At_local;       /* cbg_tile_transpose of A_local, or NULL: made at the first pull step, freed at the end */
+} cbg_bfs_params;
+typedef void (*cbg_bfs_level_fn)(void* user, int64_t level, int direction, int64_t frontier, int64_t pred);
+int cbg_grid_bfs(cbg_grid* g, const cbg_tile* A_local, int64_t gn, int64_t root, const cbg_bfs_params* p,
+                 cbg_bfs_level_fn fn, void* user, int64_t* parents, int64_t* levels);
+/* the last cbg_grid_bfs on this rank.  counts: the tree's depth (the largest level; steps run = depth + 1),
+ * reached vertices (the root included), edges traversed (the summed column lengths of the reached vertices,
+ * TopDownBFS.cpp:448-452), push steps, pull steps, push units, pull rows scanned, pull entries read (as
+ * cbg_tile_pull_max counts them); the last three are sums over the grid.  ms (may be NULL, CBG_BFS_MS_N host
+ * times): push, pull, update, communication, total.  counts[i] for i < min(n, CBG_BFS_N); returns CBG_BFS_N. */
+enum { CBG_BFS_LEVELS = 0, CBG_BFS_REACHED = 1, CBG_BFS_EDGES = 2, CBG_BFS_PUSH_STEPS = 3, CBG_BFS_PULL_STEPS = 4,
+       CBG_BFS_PUSH_UNITS = 5, CBG_BFS_PULL_ROWS = 6, CBG_BFS_PULL_ENTRIES = 7, CBG_BFS_N = 8 };
+enum { CBG_BFS_MS_PUSH = 0, CBG_BFS_MS_PULL = 1, CBG_BFS_MS_UPDATE = 2, CBG_BFS_MS_COMM = 3, CBG_BFS_MS_TOTAL = 4,
+       CBG_BFS_MS_N = 5 };
+int cbg_last_bfs_stats(int64_t* counts, int n, double* ms);
+
 /* p (HOST, n int64) = the stable argsort of key[i] = mix64(seed ^ (i * 0x9E3779B97F4A7C15)), i = 0..n-1
  * (mix64: the finalizer of cbg_tile_digest).  Equal keys keep index order.  Computed on the host.
  * This library's RandPerm (FullyDistVec::RandPerm as MCL.cpp:496-512 uses it): the
