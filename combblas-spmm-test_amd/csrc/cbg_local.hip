@@ -1076,7 +1076,9 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
       if (total > 0 && total <= cap) {
         const int f0 = __ffsll((long long)nzmask) - 1;
         const int f1 = 63 - __clzll((long long)nzmask);
-        d[0] = make_int4(R0 + (f0 << FINE_LOG), min(R0 + ((f1 + 1) << FINE_LOG), R1), 0, total);
+        // (ends as offsets from R0 / lo: in the last panel of a tile of nearly 2^31 rows the
+        // fine range's own end, R0 + 2^plog, does not fit an int)
+        d[0] = make_int4(R0 + (f0 << FINE_LOG), R0 + min((f1 + 1) << FINE_LOG, R1 - R0), 0, total);
         ns = 1;
       } else if (total > 0) {
         int run = 0, g_lo = -1, g_hi = 0, g_cnt = 0;
@@ -1084,7 +1086,7 @@ __device__ __forceinline__ void sym_pair(const SymPanelArgs& a, const SymPanelLd
           const int c = fine[f];
           if (c == 0) continue;
           const int lo = R0 + (f << FINE_LOG);
-          const int hi = min(lo + (1 << FINE_LOG), R1);
+          const int hi = lo + min(1 << FINE_LOG, R1 - lo);
           if (g_cnt && g_cnt + c > cap) {
             d[ns++] = make_int4(g_lo, g_hi, run - g_cnt, g_cnt);
             g_cnt = 0;

@@ -912,3 +912,390 @@ def aprep_piece_facts(Ah, Bp):
                 low_cond=low_cond, moved=int(moved.sum()), col_flops=f, col_big=big, col_thin=thin,
                 b_integral=bool((v == np.trunc(v)).all() and (v != 0).all() and (np.abs(v) <= 2.0 ** 24).all()),
                 b_max=float(np.abs(v).max()), b_colsum=float(colsum.max()), b_zeros=int((v == 0).sum()))
+
+
+# --------------------------------------------------------------------------
+# tall tiles (tests/test_gpu_tall_tiles.py; the routes are checked without a device in
+# tests/test_tall_tiles_cpu.py): operands whose B columns are built for one route each
+# at a given m, and the routes the documented rules give them
+#
+# The local multiply switches by the number of row panels R = ceil(m / 2^18) as well as by
+# flops and nonzeros.  tall_operands() gives every B column its own A columns, so a
+# column's flops, its products per row range and its nonzeros per row range are what
+# the spec says, whatever m is; nothing here allocates O(m).
+# --------------------------------------------------------------------------
+TALL_HASH_T = (512, 768, 1024, 1536, 2048, 3072, 4096, 6144, 8192)   # csrc/cbg_local.hip CBG_HASH_TABLES
+TALL_RANK_MIN = 683            # RANK_SLABS_MIN, GRANK_SLABS_MIN: sparse slabs of more nonzeros are ranked
+TALL_GRANK_SPAN = 1 << 22      # GRANK_SPAN_LOG: rows a group rank slab may span
+TALL_GRANK_PMAX = 4096         # GRANK_PMAX: a group's slab of more products is a hash slab (SLAB_MANYP)
+TALL_SPARSE_MAX = 4096         # SPARSE_SLAB_MAX (products of a hash-mode pair), SPARSE_NNZ_MAX (nonzeros of a hash slab)
+TALL_GROUP_TABLE = 8192        # GROUP_T: the group symbolic's table; it takes a group of products * 3 / 2 <= this
+TALL_BIG_BS = 512              # BIG_BS: B entries a group unit stages at once
+TALL_ESC_FLOPS = 512           # kSymThr[SYM_FUSED_LAST]: columns of fewer flops run expand-sort-compress
+TALL_SLAB_KEYS = 8192          # SLAB_KEYS_MAX, with 16 slab classes: (class, panel) keys while 16 R <= 8192
+TALL_BITMAP_SMALL = 3056       # SLAB_SMALL_CAP: bitmap slabs of no more nonzeros are `small` under either accumulation
+
+
+def panel_rows(m, r0, r1=None):
+    """[lo, hi): the rows of panels r0..r1 of a tile of m rows"""
+    r1 = r0 if r1 is None else r1
+    return r0 * PANEL, min((r1 + 1) * PANEL, m)
+
+
+def _distinct_rows(rng, lo, hi, n, must):
+    """n distinct rows of [lo, hi) in random order, `must` among them; no array of hi - lo entries
+    unless that is small"""
+    must = np.unique(np.asarray(must, np.int64))
+    assert len(must) <= n <= hi - lo and (len(must) == 0 or (lo <= must[0] and must[-1] < hi)), (lo, hi, n, must)
+    if hi - lo <= PANEL:
+        rest = np.setdiff1d(np.arange(lo, hi, dtype=np.int64), must)
+        rest = rng.choice(rest, n - len(must), replace=False)
+    else:
+        rest = np.zeros(0, np.int64)
+        while len(rest) < n - len(must):
+            draw = rng.integers(lo, hi, 2 * (n - len(must)) + 16)
+            rest = np.setdiff1d(np.union1d(rest, draw), must)
+        rest = rng.permutation(rest)[:n - len(must)]
+    return rng.permutation(np.concatenate([must, rest]))
+
+
+def tall_operands(m, spec, values="int", seed=0):
+    """(Ah, Bh, plan).  spec: one dict per B column, in column order:
+        route    the route the column is meant for (tall_plan's names: "copy", "esc", "small",
+                 "thin", "g64" ... "g2", "g1"); compared with the prediction in plan["routes"]
+        nb       its B entries; each is an A column of its own
+        regions  [(lo, hi, products, nnz, must), ...]: disjoint row ranges; the column has
+                 exactly `products` products in [lo, hi), on exactly min(products, nnz)
+                 distinct rows, the rows `must` among them (needs products >= nnz >= len(must)
+                 for every one of them to appear).  The products are dealt to the nb A columns
+                 in turn, each taking the next rows of the range's (shuffled) row pool
+                 cyclically: sums form wherever products > nnz.
+    The column's flops are the sum of its products.  values: `int` integers 1..4 in A and
+    1..2 in B (exact in any order; IACC), `half` the same with A + 0.5 (f32-exact, not
+    integral: the f64 slabs), `random` U(-1, 1) in both.  plan = tall_plan(Ah, Bh) with
+    plan["intended"] the spec's routes."""
+    rng = np.random.default_rng(seed)
+    acols, bcols = [], []
+    for c in spec:
+        nb = int(c["nb"])
+        rows, owner = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+        last_hi = 0
+        for lo, hi, products, nnz, must in sorted(c["regions"], key=lambda g: g[0]):
+            assert last_hi <= lo < hi <= m and len(must) <= nnz <= hi - lo, (lo, hi, nnz, last_hi, m)
+            last_hi = hi
+            base, rem = divmod(int(products), nb)
+            assert base + (1 if rem else 0) <= nnz, (c["route"], products, nb, nnz)
+            pool = _distinct_rows(rng, lo, hi, nnz, must)
+            rows.append(pool[np.arange(products) % nnz])           # one sweep over the pool, dealt in turn
+            owner.append(np.repeat(np.arange(nb), base + (np.arange(nb) < rem)))
+        rows, owner = np.concatenate(rows), np.concatenate(owner)
+        o = np.lexsort((rows, owner))
+        cut = np.searchsorted(owner[o], np.arange(nb + 1))
+        bcols.append(np.arange(len(acols), len(acols) + nb))
+        acols += [rows[o][cut[j]:cut[j + 1]] for j in range(nb)]
+    Ah = dcsc_from_cols(m, len(acols), acols)
+    Bh = dcsc_from_cols(len(acols), len(bcols), bcols)
+    Ah, Bh = tall_values(Ah, Bh, values, seed)
+    plan = tall_plan(Ah, Bh)
+    plan["intended"] = [c["route"] for c in spec]
+    return Ah, Bh, plan
+
+
+def tall_values(Ah, Bh, values, seed=0):
+    """copies of Ah, Bh with the same structure and the values of tall_operands' `values`"""
+    rng = np.random.default_rng([seed, 77])
+    na, nbs = len(Ah["ir"]), len(Bh["ir"])
+    if values == "random":
+        av, bv = rng.uniform(-1.0, 1.0, na), rng.uniform(-1.0, 1.0, nbs)
+    else:
+        assert values in ("int", "half"), values
+        av = rng.integers(1, 5, na).astype(np.float64) + (0.5 if values == "half" else 0.0)
+        bv = rng.integers(1, 3, nbs).astype(np.float64)
+    return dict(Ah, val=av), dict(Bh, val=bv)
+
+
+def tall_sparse_class(nnz, span, products=0, group=False):
+    """csrc/cbg_local.hip slab_class for a sparse (hash-mode) slab: a rank slab above
+    TALL_RANK_MIN nonzeros where it spans one panel; a group rank slab above it where it is a
+    group's slab of <= TALL_GRANK_PMAX products spanning <= 2^22 rows; else the smallest hash
+    table of load <= 2/3"""
+    if nnz > TALL_RANK_MIN and span <= PANEL:
+        return "rank_N%d" % (1024 if nnz <= 1024 else 2048 if nnz <= 2048 else 4096)
+    if nnz > TALL_RANK_MIN and group and products <= TALL_GRANK_PMAX and PANEL < span <= TALL_GRANK_SPAN:
+        return "group_rank_N%d" % (2048 if nnz <= 2048 else 4096)
+    return "hash_T%d" % next((t for t in TALL_HASH_T if 2 * t >= 3 * nnz), TALL_HASH_T[-1])
+
+
+def thin_key_bits(m, nthin):
+    """csrc/cbg_thin.hip thin_any: bits of a (column, row) key; 32-bit keys while they are <= 32"""
+    rowbits = colbits = 1
+    while (1 << rowbits) < m:
+        rowbits += 1
+    while (1 << colbits) < nthin:
+        colbits += 1
+    return rowbits + colbits
+
+
+def tall_plan(Ah, Bh):
+    """The routes the documented rules of csrc/cbg_local.hip / cbg_thin.hip give every stored B
+    column of A * B, for m > 2^22 rows (the big cut is then 4096 flops), from the oracle's flops
+    per column and the operands themselves; no device.
+
+    Column routes (k_classify; plan_symbolic_bins): one B entry: "copy"; flops <= 512: "esc";
+    <= 4096: "small"; above, with R >= 4 and flops * 4 < entries * R: "thin"; else the first
+    group size g = 64, 32 ... 2 with g <= R and flops <= 4096 * R // g: "g<g>"; else "g1".
+
+    Units (sym_big_columns, k_sym_panel, sym_group, sym_pair): a column of class g has
+    ceil(R / g) units of panels [r0, min(r0 + g, R) - 1], counted in sym_group_units (g > 1)
+    or sym_panel_units (g = 1) whether or not any product falls into them.  A group unit is
+    handed to k_sym_deferred (sym_deferred_units), which runs its panels one by one, when it
+    is a single panel (the ragged last group: r1 == r0, empty or not), when the column has
+    more than 512 B entries, when its products * 3 / 2 exceed the 8192-slot table (products >
+    5461) or when its nonzeros exceed 4096; else, if it has any nonzero, it is ONE sparse slab
+    over the group's rows, filed under its first panel.  A single panel (class g1 or deferred)
+    with <= 512 B entries and <= 4096 products is one sparse slab over the panel's rows; with
+    more it is a bitmap pair (here: of <= 3056 nonzeros, one `bitmap_small` slab).  A sparse
+    slab's launch class: tall_sparse_class."""
+    m = int(Ah["m"])
+    assert m > TALL_GRANK_SPAN, "the lower big-column cut (m <= 2^22) is not restated here"
+    R = (m + PANEL - 1) // PANEL
+    f = np.asarray(oracle_symbolic(Ah, Bh)[0], np.int64)
+    ne = np.diff(Bh["cp"]).astype(np.int64)
+    classes = [g for g in (64, 32, 16, 8, 4, 2) if g <= R]
+    acp = np.asarray(Ah["cp"], np.int64)
+    aslot = np.full(Ah["n"], -1, np.int64)
+    aslot[Ah["jc"]] = np.arange(len(Ah["jc"]))
+    routes, groups = [], {}
+    slabs, keys = {}, []
+    units = dict(sym_group_units=0, sym_panel_units=0, sym_deferred_units=0)
+
+    def add_slab(cls, panel):
+        slabs[cls] = slabs.get(cls, 0) + 1
+        keys.append((cls, panel))
+
+    def single_panel(rows, r, nb):
+        pr = rows[(rows >> 18) == r]
+        if len(pr) == 0:
+            return
+        z = len(np.unique(pr))
+        lo, hi = panel_rows(m, r)
+        if nb <= TALL_BIG_BS and len(pr) <= TALL_SPARSE_MAX:
+            add_slab(tall_sparse_class(z, hi - lo), r)
+        else:
+            assert z <= TALL_BITMAP_SMALL, "bitmap pairs of more than one small slab are not restated here"
+            add_slab("bitmap_small", r)
+
+    for j in range(len(ne)):
+        F, nb = int(f[j]), int(ne[j])
+        if nb == 1:
+            routes.append("copy")
+        elif F <= TALL_ESC_FLOPS:
+            routes.append("esc")
+        elif F <= BIG_FLOPS:
+            routes.append("small")
+        elif R >= 4 and F * THIN_RATIO < nb * R:
+            routes.append("thin")
+        else:
+            g = next((g for g in classes if F <= GROUP_PRODUCTS * R // g), 1)
+            routes.append("g%d" % g)
+            ks = aslot[Bh["ir"][Bh["cp"][j]:Bh["cp"][j + 1]]]
+            ks = ks[ks >= 0]
+            rows = np.concatenate([Ah["ir"][acp[k]:acp[k + 1]] for k in ks]).astype(np.int64)
+            assert len(rows) == F
+            ng = (R + g - 1) // g
+            units["sym_group_units" if g > 1 else "sym_panel_units"] += ng
+            glist = []
+            for q in range(ng):
+                r0, r1 = q * g, min(q * g + g, R) - 1
+                lo, hi = panel_rows(m, r0, r1)
+                gr = rows[(rows >= lo) & (rows < hi)]
+                P, Z = len(gr), len(np.unique(gr))
+                if g == 1:
+                    single_panel(gr, r0, nb)
+                    out = "panel"
+                elif r1 == r0 or nb > TALL_BIG_BS or 3 * P > 2 * TALL_GROUP_TABLE or Z > TALL_SPARSE_MAX:
+                    units["sym_deferred_units"] += 1
+                    for r in range(r0, r1 + 1):
+                        single_panel(gr, r, nb)
+                    out = "deferred"
+                elif Z > 0:
+                    out = tall_sparse_class(Z, hi - lo, P, group=True)
+                    add_slab(out, r0)
+                else:
+                    out = "empty"
+                glist.append((r0, r1, P, Z, out))
+            groups[j] = glist
+    routes = np.array(routes)
+    nthin = int((routes == "thin").sum())
+    big = np.array([r[0] == "g" for r in routes])
+    return dict(R=R, routes=list(routes), flops=f, entries=ne, groups=groups, slabs=slabs, slab_keys=keys,
+                n_slabs=len(keys), n_big=int(big.sum()), thin_columns=nthin, esc_columns=int((routes == "esc").sum()),
+                small_columns=int((routes == "small").sum()), copy_columns=int((routes == "copy").sum()),
+                class_columns={g: int((routes == "g%d" % g).sum()) for g in classes + [1]},
+                thin_key_bits=thin_key_bits(m, nthin) if nthin else 0,
+                slab_keys_by_panel=16 * R <= TALL_SLAB_KEYS, **units)
+
+
+def _ends(lo, hi, *more):
+    return [lo, hi - 1] + [r for r in more if lo <= r < hi]
+
+
+def _group_regions(m, g, cells, full_panels, tail=None):
+    """regions of a column taken in groups of g panels: cells = {group: (products, nnz)} over the
+    first `full_panels` panels, each group's first and last row among its rows; `tail`
+    (products, nnz): the rows from panel `full_panels` on (the ragged last panel), if the tile has any"""
+    out = []
+    for q, (P, Z) in sorted(cells.items()):
+        lo, hi = panel_rows(m, q * g, q * g + g - 1)
+        assert hi == (q + 1) * g * PANEL <= full_panels * PANEL
+        out.append((lo, hi, P, Z, _ends(lo, hi)))
+    if tail and m > full_panels * PANEL:
+        lo = full_panels * PANEL
+        out.append((lo, m, tail[0], min(tail[1], m - lo), _ends(lo, m)))
+    return out
+
+
+def tall_spec_65(m=(1 << 24) + 77):
+    """R = 65: the 64-panel class holds the columns of 4097..4160 flops (4096 * 65 // 64), as
+    panels 0..63 and the lone ragged panel 64 (77 rows), which is always a deferred unit"""
+    assert (m + PANEL - 1) // PANEL == 65
+    G, H2 = 1 << 24, 1 << 23
+    anywhere = lambda P, Z: [(0, m, P, Z, _ends(0, m))]
+    return [
+        # the class's upper edge: 4110 products (> 4096: SLAB_MANYP) on 1500 rows of the group, 50 in panel 64
+        dict(route="g64", nb=50, regions=[(0, G, 4110, 1500, _ends(0, G)), (G, m, 50, 40, _ends(G, m))]),
+        # its lower edge; nothing in panel 64 (an empty deferred unit); 700 nonzeros over 2^24 rows stay a hash slab
+        dict(route="g64", nb=40, regions=[(0, G, 4097, 700, _ends(0, G))]),
+        # only rows of panel 64: an empty group, and 4130 products on 77 rows in the deferred panel (a bitmap pair)
+        dict(route="g64", nb=60, regions=[(G, m, 4130, 77, _ends(G, m))]),
+        # the control: 32-panel groups (4161..8320 flops), at its lower edge and inside
+        dict(route="g32", nb=40, regions=[(0, H2, 2100, 500, _ends(0, H2)), (H2, G, 2061, 684, _ends(H2, G))]),
+        dict(route="g32", nb=100, regions=[(0, H2, 3900, 1200, _ends(0, H2)), (H2, G, 3900, 700, _ends(H2, G)),
+                                           (G, m, 200, 60, _ends(G, m))]),
+        dict(route="thin", nb=400, regions=anywhere(4200, 1500)),
+        dict(route="small", nb=20, regions=anywhere(3000, 2000)),
+        dict(route="esc", nb=3, regions=anywhere(300, 200)),
+        dict(route="copy", nb=1, regions=anywhere(500, 500)),
+    ]
+
+
+def tall_spec_512(m):
+    """m = 2^27 (R = 512: the slab list keyed by class and panel) or 2^27 + 5 (R = 513: by class
+    alone; the last group of every class is the 5-row panel 512, a deferred unit): one column
+    per group class 64 .. 4 with its flops in the upper half of the class's range, every full
+    group populated with <= 4096 products, its first and last row included; a second 16-panel
+    column with the groups that leave the group path"""
+    R = (m + PANEL - 1) // PANEL
+    assert R in (512, 513) and m >= (1 << 27)
+    tail = (10, 5)
+    z16 = (683, 684, 2048, 2049)     # the group rank classes' edges: hash_T1536 | N2048 | N2048 | N4096
+    odd = {q: (3750, 1200) for q in range(21)}
+    odd.update({21: (4500, 2500),    # > 4096 products: no group rank slab (a hash slab)
+                22: (6000, 3000),    # > 5461 products: deferred, 16 single panels
+                23: (5461, 4096),    # the largest group the table takes, the most nonzeros of a hash slab
+                24: (5462, 1000),    # one product more: deferred
+                25: (5000, 4097)})   # one nonzero more: deferred
+    anywhere = lambda P, Z: [(0, m, P, Z, _ends(0, m))]
+    return [
+        dict(route="g64", nb=64, regions=_group_regions(m, 64, {q: (3750, 800) for q in range(8)}, 512, tail)),
+        dict(route="g32", nb=100, regions=_group_regions(m, 32, {q: (3750, 1000) for q in range(16)}, 512, tail)),
+        dict(route="g16", nb=128, regions=_group_regions(m, 16, {q: (3750, z16[q % 4]) for q in range(32)}, 512, tail)),
+        dict(route="g16", nb=128, regions=_group_regions(m, 16, odd, 512, tail)),
+        dict(route="g8", nb=200, regions=_group_regions(m, 8, {q: (3900, 1500) for q in range(64)}, 512, tail)),
+        dict(route="g4", nb=256, regions=_group_regions(m, 4, {q: (3900, 2500) for q in range(128)}, 512, tail)),
+        dict(route="esc", nb=4, regions=anywhere(400, 300)),
+        dict(route="esc", nb=2, regions=anywhere(512, 256)),
+        dict(route="esc", nb=3, regions=anywhere(40, 30)),
+        dict(route="small", nb=20, regions=anywhere(3000, 2000)),
+        dict(route="small", nb=2, regions=anywhere(513, 300)),
+        dict(route="small", nb=8, regions=anywhere(4096, 1000)),
+        dict(route="copy", nb=1, regions=anywhere(100, 100)),
+    ]
+
+
+TALL_MAX_M = (1 << 31) - 2     # the tallest tile the ABI admits (m < INT32_MAX)
+
+
+def tall_spec_8192(m=TALL_MAX_M):
+    """m = 2^31 - 2 (R = 8192, row ids up to 2^31 - 3): three 64-panel-class big columns
+    (flops <= 524288; not thin: flops >= 2048 x entries), three thin columns (64-bit keys: 31 row
+    bits), ESC, block-hash and single-entry columns; rows 0, 2^31 - 2^18 - 1, m - 2 and m - 1"""
+    R = (m + PANEL - 1) // PANEL
+    assert R == 8192
+    last = (R - 1) * PANEL          # first row of the last panel (2^18 - 2 rows)
+    edge = [0, last - 1, m - 2, m - 1]
+
+    def groups(qs, P, Z):
+        out = []
+        for q in qs:
+            lo, hi = panel_rows(m, 64 * q, 64 * q + 63)
+            out.append((lo, hi, P, Z, _ends(lo, hi, *edge)))
+        return out
+
+    anywhere = lambda P, Z: [(0, m, P, Z, edge)]
+    qa = [0, 1, 2, 3] + list(range(8, 128, 6)) + [126, 127]
+    qb = list(range(5, 125, 6))
+    return [
+        dict(route="g64", nb=40, regions=groups(qa, 3840, 1000)),
+        # the last group's products all in the last panel, > 5461 of them: deferred, and there a bitmap pair
+        # whose last fine range ends past 2^31
+        dict(route="g64", nb=40, regions=groups(qb, 3840, 684) + [(last, m, 6000, 2000, [last, m - 2, m - 1])]),
+        dict(route="g64", nb=48, regions=groups(qa[1:] + [4], 3840, 3000)),
+        dict(route="thin", nb=8, regions=anywhere(5000, 3000)),
+        dict(route="thin", nb=9, regions=anywhere(4097, 1000)),
+        dict(route="thin", nb=300, regions=anywhere(6000, 1500)),
+        dict(route="esc", nb=3, regions=anywhere(300, 200)),
+        dict(route="esc", nb=2, regions=anywhere(512, 256)),
+        dict(route="esc", nb=5, regions=anywhere(9, 4)),
+        dict(route="small", nb=10, regions=anywhere(2000, 1500)),
+        dict(route="copy", nb=1, regions=anywhere(300, 300)),
+        dict(route="copy", nb=1, regions=anywhere(5000, 5000)),     # more flops than the big cut: the chunked copy
+    ]
+
+
+_TALL_CACHE = {}
+
+
+def tall_case(name):
+    """(Ah, Bh, plan) of a named case with the `int` values, built once: r65, r512, r513, r8192"""
+    if name not in _TALL_CACHE:
+        m, spec = {"r65": ((1 << 24) + 77, tall_spec_65), "r512": (1 << 27, tall_spec_512),
+                   "r513": ((1 << 27) + 5, tall_spec_512), "r8192": (TALL_MAX_M, tall_spec_8192)}[name]
+        _TALL_CACHE[name] = tall_operands(m, spec(m), "int", seed=sorted(("r65", "r512", "r513", "r8192")).index(name))
+    return _TALL_CACHE[name]
+
+
+def tall_reference(name, values, sr):
+    """(A, B, oracle's C) of a named case under `values`, computed once, shared, left unchanged"""
+    key = (name, values, sr)
+    if key not in _TALL_CACHE:
+        Ah, Bh, _ = tall_case(name)
+        A, B = (Ah, Bh) if values == "int" else tall_values(Ah, Bh, values)
+        _TALL_CACHE[key] = (A, B, oracle_local(A, B, sr))
+    return _TALL_CACHE[key]
+
+
+def thin_key_operands(m, nthin, arows):
+    """nthin thin columns and nothing else, for the thin pass's key width (32-bit keys while
+    rowbits(m) + colbits(nthin) <= 32).  Unlike tall_operands the B columns SHARE A's columns:
+    the inline path (A's columns of one or two rows held in the column map's records) is taken
+    where nnz(A) <= 2 x A's stored columns and the flops are >= 4 nnz(A), so every A entry has
+    to be used several times.  arows = 2: A has 3000 columns of one and two rows alternately
+    and every B column 2900 of them (>= 4300 flops); arows = 8: 700 columns of 8 rows, 600 per B
+    column (4800 flops).  Rows come from a pool of 1500 (0, 2^27 - 1 and m - 1 among them): the
+    products of a column collide.  Integer values (exact in any order)."""
+    rng = np.random.default_rng([m % 1000, nthin, arows])
+    K, nb = (3000, 2900) if arows == 2 else (700, 600)
+    must = np.unique([0, (1 << 27) - 1, m - 1])
+    pool = _distinct_rows(rng, 0, m, 1500, must)
+    rest = np.setdiff1d(pool, must)
+    lens = (1 + np.arange(K) % 2) if arows == 2 else np.full(K, arows)
+    acols = [np.sort(rng.choice(pool, L, replace=False)) for L in lens]
+    special = 1 + 2 * np.arange(len(must))    # columns 1, 3, 5 (two rows where arows = 2) hold the edge rows
+    for k, r in zip(special, must):
+        acols[k] = np.sort(np.append(rng.choice(rest, lens[k] - 1, replace=False), r))
+    others = np.setdiff1d(np.arange(K), special)
+    bcols = [np.sort(np.append(rng.choice(others, nb - len(special), replace=False), special)) for _ in range(nthin)]
+    Ah = dcsc_from_cols(m, K, acols, rng.integers(1, 5, int(lens.sum())).astype(np.float64))
+    Bh = dcsc_from_cols(K, nthin, bcols, rng.integers(1, 3, nthin * nb).astype(np.float64))
+    return Ah, Bh
