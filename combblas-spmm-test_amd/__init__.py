@@ -17,6 +17,8 @@ It mirrors the reference's operator surface for the path:
   PSpGEMM (SpParMat.h:454-467)                     PSpGEMM(A, B, sr)
   DistEdgeList::GenGraph500Data + SpParMat(DEL)    rmat_tile / SpParMat.rmat
      + RemoveLoops
+  SpMV<SR> dense / sparse (ParFriends.h:1922,      SpMV(A, x, sr) / SpMV_sparse(A, xind, xval, sr)
+     1892), SR PlusTimes or MinPlus on double         (SpMSpV is the SelectMax tile product of the BFS)
 
 The reference MPI_Aborts on misuse; here the same codes surface as CbgError.code
 (3001 GRIDMISMATCH, 3002 DIMMISMATCH, 3003 NOTSQUARE, 3005 MATRIXALIAS).
@@ -92,6 +94,7 @@ EXPORTS = [
     "cbg_grid_hipmcl_prepared", "cbg_grid_nonisolated",
     "cbg_tile_ewise", "cbg_ewise_bounds", "cbg_last_ewise_stats", "cbg_grid_betwcent", "cbg_last_betwcent_stats",
     "cbg_tile_spmspv_max", "cbg_tile_pull_max", "cbg_bfs_bounds", "cbg_grid_bfs", "cbg_last_bfs_stats",
+    "cbg_tile_spmv", "cbg_tile_spmspv", "cbg_grid_spmv", "cbg_grid_spmspv", "cbg_spmv_bounds", "cbg_last_spmv_stats",
 ]
 RED_SUM, RED_MAX, RED_SUMSQ, RED_COUNT = 0, 1, 2, 3  # cbg_grid_reduce_cols
 _REDS = {"sum": RED_SUM, "plus": RED_SUM, "max": RED_MAX, "maximum": RED_MAX, "sumsq": RED_SUMSQ, "count": RED_COUNT}
@@ -249,6 +252,12 @@ def lib():
         "cbg_bfs_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_grid_bfs": ([vp, T, i64, i64, ctypes.POINTER(CBfsParams), BFS_LEVEL_FN, vp, vp, vp], i32),
         "cbg_last_bfs_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
+        "cbg_tile_spmv": ([T, T, i32, vp, vp, i32, vp], i32),
+        "cbg_tile_spmspv": ([T, i32, vp, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
+        "cbg_grid_spmv": ([vp, T, T, i64, i64, i32, vp, vp], i32),
+        "cbg_grid_spmspv": ([vp, T, i64, i64, i32, vp, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
+        "cbg_spmv_bounds": ([ctypes.POINTER(i64), i32], i32),
+        "cbg_last_spmv_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_spref_sort_bounds": ([ctypes.POINTER(i64), i32], i32),
         "cbg_last_spref_stats": ([ctypes.POINTER(i64), i32, ctypes.POINTER(ctypes.c_double)], i32),
         "cbg_grid_nonisolated": ([vp, T, i64, vp, ctypes.POINTER(i64)], i32),
@@ -428,6 +437,35 @@ class Tile:
         _check(lib().cbg_tile_pull_max(ctypes.byref(self.c), x.ctypes.data, nx, sk.ctypes.data if sk is not None else None,
                                        yi.ctypes.data, yv.ctypes.data, ctypes.byref(ny), ctypes.byref(er)))
         return yi[:ny.value].copy(), yv[:ny.value].copy(), int(er.value)
+
+    def spmv(self, x, sr=PLUS_TIMES, At=None):
+        """y = self * x for a dense x of n doubles on PlusTimesSRing or MinPlusSRing (cbg_tile_spmv) -> m doubles.
+        At: self.transpose(), made for the call when None.  A row without a stored entry gives the
+        semiring's id (0.0, DBL_MAX).  The order of a row's sum: include/cbg.h, tests/spmv_ref.py."""
+        xa = np.ascontiguousarray(x, np.float64).ravel()
+        if len(xa) != self.n:
+            raise CbgError(INVALIDPARAMS, "spmv: x has one value per column")
+        if len(xa) == 0:
+            xa = np.zeros(1)
+        y = np.zeros(max(self.m, 1))
+        _check(lib().cbg_tile_spmv(ctypes.byref(self.c), ctypes.byref(At.c) if At is not None else None, _sr(sr),
+                                   xa.ctypes.data, y.ctypes.data, 0, None))
+        return y[:self.m]
+
+    def spmspv(self, xind, xval, sr=PLUS_TIMES):
+        """y = self * x for a sparse x (cbg_tile_spmspv): xind ascending distinct local columns, xval their
+        doubles -> (yind ascending, yval), one entry per row with a product (a cancelled sum is a stored 0.0)"""
+        xi, nx = _index_arg(np.asarray(xind, np.int64))
+        xv = np.ascontiguousarray(xval, np.float64).ravel()
+        if len(xv) != nx:
+            raise CbgError(INVALIDPARAMS, "spmspv: xval has one value per index")
+        if len(xv) == 0:
+            xv = np.zeros(1)
+        yi, yv = np.zeros(max(self.m, 1), np.int64), np.zeros(max(self.m, 1))
+        ny = ctypes.c_int64()
+        _check(lib().cbg_tile_spmspv(ctypes.byref(self.c), _sr(sr), xi.ctypes.data, xv.ctypes.data, nx, yi.ctypes.data,
+                                     yv.ctypes.data, ctypes.byref(ny)))
+        return yi[:ny.value].copy(), yv[:ny.value].copy()
 
     def split_cols(self, cut):
         """SpDCCols::Split (SpDCCols.cpp:905-930)"""
@@ -1567,6 +1605,54 @@ def SpMSpV(tile, xind, xval=None):
     _check(lib().cbg_tile_spmspv_max(ctypes.byref(tile.c), x.ctypes.data, v.ctypes.data if v is not None else None, nx,
                                      yi.ctypes.data, yv.ctypes.data, ctypes.byref(ny)))
     return yi[:ny.value].copy(), yv[:ny.value].copy()
+
+
+def SpMV(A, x, sr=PlusTimesSRing, At=None):
+    """SpMV<SR>(A, x) with a dense vector (ParFriends.h:1860-1990, cbg_grid_spmv): x gn doubles, the same on
+    every rank -> y, gm doubles, the same on every rank.  sr PlusTimesSRing or MinPlusSRing.  At: the Tile
+    A.tile.transpose() (None: made for the call).  Any pr x pc grid.  Collective."""
+    xa = np.ascontiguousarray(x, np.float64).ravel()
+    if len(xa) != A.gn:
+        raise CbgError(INVALIDPARAMS, "SpMV: x has one value per global column")
+    if len(xa) == 0:
+        xa = np.zeros(1)
+    y = np.zeros(max(A.gm, 1))
+    at = At.tile if isinstance(At, SpParMat) else At
+    _check(lib().cbg_grid_spmv(A.grid.h, ctypes.byref(A.tile.c), ctypes.byref(at.c) if at is not None else None,
+                               A.gm, A.gn, _sr(sr), xa.ctypes.data, y.ctypes.data))
+    return y[:A.gm]
+
+
+def SpMV_sparse(A, xind, xval, sr=PlusTimesSRing):
+    """SpMV<SR>(A, x) with a sparse vector (cbg_grid_spmspv): xind ascending distinct global ids, xval their
+    doubles, the same on every rank -> (yind ascending, yval), the same on every rank.  Collective."""
+    xi, nx = _index_arg(np.asarray(xind, np.int64))
+    xv = np.ascontiguousarray(xval, np.float64).ravel()
+    if len(xv) != nx:
+        raise CbgError(INVALIDPARAMS, "SpMV_sparse: xval has one value per index")
+    if len(xv) == 0:
+        xv = np.zeros(1)
+    yi, yv = np.zeros(max(A.gm, 1), np.int64), np.zeros(max(A.gm, 1))
+    ny = ctypes.c_int64()
+    _check(lib().cbg_grid_spmspv(A.grid.h, ctypes.byref(A.tile.c), A.gm, A.gn, _sr(sr), xi.ctypes.data, xv.ctypes.data,
+                                 nx, yi.ctypes.data, yv.ctypes.data, ctypes.byref(ny)))
+    return yi[:ny.value].copy(), yv[:ny.value].copy()
+
+
+def spmv_bounds():
+    """[16, 4096, C] (cbg_spmv_bounds): the longest rows of the 16-lane and the wave class (4096 is also the
+    chunk of the longer ones), and the entries of a column of x one unit of the sparse product expands"""
+    b = (ctypes.c_int64 * 3)()
+    n = lib().cbg_spmv_bounds(b, 3)
+    return [int(v) for v in b[:n]]
+
+
+def spmv_stats():
+    """the last SpMV / SpMV_sparse / Tile.spmv / Tile.spmspv on this thread (cbg_last_spmv_stats)"""
+    c, ms = (ctypes.c_int64 * 7)(), ctypes.c_double()
+    lib().cbg_last_spmv_stats(c, 7, ctypes.byref(ms))
+    return dict(rows_group=int(c[0]), rows_wave=int(c[1]), rows_long=int(c[2]), chunks=int(c[3]), units=int(c[4]),
+                products=int(c[5]), entries_out=int(c[6]), ms=ms.value)
 
 
 def bfs_bounds():

@@ -49,6 +49,10 @@ int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn
                   const cbg_betwcent_params& P, cbg_betwcent_level_fn fn, void* user, double* bc);
 int grid_bfs(cbg_grid* g, const cbg_tile& A, int64_t gn, int64_t root, const cbg_bfs_params& P, cbg_bfs_level_fn fn,
              void* user, int64_t* parents, int64_t* levels);
+int grid_spmv(cbg_grid* g, const cbg_tile* A, const cbg_tile* At, int64_t gm, int64_t gn, int sr, const double* x,
+              double* y);
+int grid_spmspv(cbg_grid* g, const cbg_tile& A, int64_t gm, int64_t gn, int sr, const int64_t* xind, const double* xval,
+                int64_t nx, int64_t* yind, double* yval, int64_t* ny);
 void rand_perm(int64_t n, uint64_t seed, int64_t* p);
 int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids);
 int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
@@ -990,6 +994,109 @@ int cbg_last_bfs_stats(int64_t* counts, int n, double* ms) {
   for (int i = 0; counts && i < n && i < CBG_BFS_N; ++i) counts[i] = b.counts[i];
   for (int i = 0; ms && i < CBG_BFS_MS_N; ++i) ms[i] = b.ms[i];
   return CBG_BFS_N;
+}
+
+// ---------------- matrix x vector on PlusTimes and MinPlus ----------------
+static bool spmv_sr_ok(int sr) { return sr == CBG_PLUS_TIMES || sr == CBG_MIN_PLUS; }
+// the checks the tile and the grid product share; 0 or the code (the message is set)
+static int spmv_dense_args(const cbg_tile* A, const cbg_tile* At, int sr, const double* x, double* y) {
+  if (!A && !At) return fail(CBG_ERR_INVALIDPARAMS, "spmv: A and At are both NULL");
+  if (A)
+    if (int rc = check_tile(A, true, "A")) return rc;
+  if (At)
+    if (int rc = check_tile(At, true, "At")) return rc;
+  if (!spmv_sr_ok(sr)) return fail(CBG_ERR_INVALIDPARAMS, "spmv: the semiring is CBG_PLUS_TIMES or CBG_MIN_PLUS");
+  const int64_t m = A ? A->m : At->n, n = A ? A->n : At->m;
+  if ((m > 0 && !y) || (n > 0 && !x)) return fail(CBG_ERR_INVALIDPARAMS, "spmv: x or y is NULL");
+  if (A && At && (At->m != A->n || At->n != A->m))
+    return fail(CBG_ERR_DIMMISMATCH, "spmv: At does not have the shape of A's transpose");
+  return CBG_OK;
+}
+
+int cbg_tile_spmv(const cbg_tile* A, const cbg_tile* At, int semiring, const double* x, double* y, int on_device,
+                  void* hip_stream) {
+  if (int rc = spmv_dense_args(A, At, semiring, x, y)) return rc;
+  return guard([&] {
+    cbg::spmv_stats_reset();
+    const int64_t m = A ? A->m : At->n, n = A ? A->n : At->m;
+    const int64_t nnz = At ? At->nnz : A->nnz;
+    hipStream_t s = as_stream(hip_stream);
+    if (nnz == 0 && !on_device) {  // an empty tile: id everywhere, no kernel
+      for (int64_t i = 0; i < m; ++i) y[i] = cbg::spmv_identity(semiring);
+      return (int)CBG_OK;
+    }
+    cbg::TileGuard own;
+    if (!At) {
+      cbg::tile_transpose(*A, own.t, s);
+      CBG_HIP(hipStreamSynchronize(s));
+      At = &own.t;
+    }
+    if (on_device) {
+      cbg::tile_spmv_device(*At, semiring, x, y, s);
+      if (own.t.cp) (void)cbg::spmv_stats();  // the transpose made here is freed on return: wait for the product
+      return (int)CBG_OK;
+    }
+    cbg::DBuf<double> dx(std::max<int64_t>(n, 1)), dy(std::max<int64_t>(m, 1));
+    struct Wait {  // declared after the buffers, so it runs first
+      hipStream_t s;
+      ~Wait() { (void)hipStreamSynchronize(s); }
+    } wait{s};
+    if (n > 0) CBG_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    cbg::tile_spmv_device(*At, semiring, dx.p, dy.p, s);
+    if (m > 0) CBG_HIP(hipMemcpyAsync(y, dy.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    CBG_HIP(hipStreamSynchronize(s));
+    (void)cbg::spmv_stats();
+    return (int)CBG_OK;
+  });
+}
+
+int cbg_tile_spmspv(const cbg_tile* A, int semiring, const int64_t* xind, const double* xval, int64_t nx,
+                    int64_t* yind, double* yval, int64_t* ny) {
+  if (int rc = check_tile(A, true, "A")) return rc;
+  if (!spmv_sr_ok(semiring)) return fail(CBG_ERR_INVALIDPARAMS, "spmspv: the semiring is CBG_PLUS_TIMES or CBG_MIN_PLUS");
+  if (!ny || (A->m > 0 && (!yind || !yval))) return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_spmspv: an output is NULL");
+  if (!bfs_index_ok(xind, nx, A->n) || (nx > 0 && !xval))
+    return fail(CBG_ERR_INVALIDPARAMS, "cbg_tile_spmspv: xind holds nx >= 0 distinct ascending columns below A->n, xval their values");
+  return guard([&] {
+    cbg::spmv_stats_reset();
+    cbg::tile_spmspv(*A, semiring, xind, xval, nx, yind, yval, ny, default_stream());
+    return CBG_OK;
+  });
+}
+
+int cbg_grid_spmv(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* At_local, int64_t gm, int64_t gn, int semiring,
+                  const double* x, double* y) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = spmv_dense_args(A_local, At_local, semiring, x, y);
+  if (!arg && (gm < 0 || gn < 0 || (gm > 0 && !y) || (gn > 0 && !x)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_spmv: gm, gn >= 0, x and y are needed");
+  return grid_call(g, arg, [&] { return cbg::grid_spmv(g, A_local, At_local, gm, gn, semiring, x, y); });
+}
+
+int cbg_grid_spmspv(cbg_grid* g, const cbg_tile* A_local, int64_t gm, int64_t gn, int semiring, const int64_t* xind,
+                    const double* xval, int64_t nx, int64_t* yind, double* yval, int64_t* ny) {
+  if (!g) return fail(CBG_ERR_INVALIDPARAMS, "grid is NULL");
+  int arg = check_tile(A_local, true, "A");
+  if (!arg && !spmv_sr_ok(semiring))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "spmspv: the semiring is CBG_PLUS_TIMES or CBG_MIN_PLUS");
+  if (!arg && (gm < 0 || gn < 0 || !ny || (gm > 0 && (!yind || !yval))))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_spmspv: gm, gn >= 0 and the outputs are needed");
+  if (!arg && (!bfs_index_ok(xind, nx, gn) || (nx > 0 && !xval)))
+    arg = fail(CBG_ERR_INVALIDPARAMS, "cbg_grid_spmspv: xind holds nx >= 0 distinct ascending ids below gn, xval their values");
+  return grid_call(g, arg, [&] {
+    return cbg::grid_spmspv(g, *A_local, gm, gn, semiring, xind, xval, nx, yind, yval, ny);
+  });
+}
+
+int cbg_spmv_bounds(int64_t* bounds, int n) { return cbg::spmv_bounds(bounds, n); }
+
+int cbg_last_spmv_stats(int64_t* counts, int n, double* ms) {
+  return guard([&] {
+    const cbg::SpmvStats& b = cbg::spmv_stats();
+    for (int i = 0; counts && i < n && i < CBG_SPMV_N; ++i) counts[i] = b.counts[i];
+    if (ms) *ms = b.ms;
+    return (int)CBG_SPMV_N;
+  });
 }
 
 int cbg_rand_perm(int64_t n, uint64_t seed, int64_t* p) {

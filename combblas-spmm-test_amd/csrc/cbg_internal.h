@@ -497,6 +497,29 @@ void bfs_assemble_bits(const u64* all, int pr, int64_t per, int64_t wb, int64_t 
 void bfs_compact(const u64* bits, int64_t coff, int64_t ln, const int64_t* len, int32_t* fl, int64_t* nu,
                  int64_t* scratch, u64* stat, hipStream_t s, DeferredFree& df);
 
+// y = A x on PlusTimes and MinPlus over a dense or a sparse vector (cbg_spmv.hip)
+struct SpmvStats {
+  int64_t counts[CBG_SPMV_N] = {};
+  double ms = 0;
+};
+SpmvStats& spmv_stats();  // the calling thread's, summed since the last reset; waits for a product still running
+void spmv_stats_reset();
+int spmv_bounds(int64_t* bounds, int n);
+double spmv_identity(int sr);  // the reference's SR::id(): 0.0, DBL_MAX
+void spmv_fill_device(double* y, int64_t n, double v, hipStream_t s);
+// y (device, At.n) = A x with At = A's transpose and x (device, At.m): queued on s, nothing waits.  The
+// call's temporaries return to the pool when the thread's next product starts or its statistics are read.
+void tile_spmv_device(const cbg_tile& At, int sr, const double* x, double* y, hipStream_t s);
+// y[i] = all[i] + all[lm + i] + ... over the P blocks in order (SR::add)
+void spmv_combine_device(double* y, const double* all, int P, int64_t lm, int sr, hipStream_t s);
+// host vectors in and out; synchronizes s
+void tile_spmspv(const cbg_tile& A, int sr, const int64_t* xind, const double* xval, int64_t nx, int64_t* yind,
+                 double* yval, int64_t* ny, hipStream_t s);
+// n partial entries (rows below m) concatenated in rank order -> one entry per row, the row's entries folded in
+// that order; host arrays; returns the entries out
+int64_t spmspv_combine(const int64_t* ind, const double* val, int64_t n, int64_t m, int sr, int64_t* oind, double* oval,
+                       hipStream_t s);
+
 // measured HBM bandwidth: 16-B-per-lane device copy (cbg_ops.hip)
 double hbm_copy_gbps(int64_t bytes, int reps);
 void store_probe(int64_t bytes, int width);

@@ -2462,6 +2462,153 @@ int grid_bfs(cbg_grid* g, const cbg_tile& A, int64_t gn, int64_t root, const cbg
   return CBG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// SpMV<SR> over a dense or a sparse vector (ParFriends.h:1860-1990), any pr x pc grid.  The vectors are
+// replicated: every rank holds x and receives y.  A rank multiplies its tile by its column block's slice of
+// x (cbg_spmv.hip); the results of a grid row's ranks are combined with SR::add in grid-column order, and the
+// row blocks are gathered along the grid column.  The reference's dense SpMV exchanges the vector with the
+// complement rank of a square grid; here nothing is exchanged before the product.
+// ---------------------------------------------------------------------------
+int grid_spmv(cbg_grid* g, const cbg_tile* A, const cbg_tile* At, int64_t gm, int64_t gn, int sr, const double* x,
+              double* y) {
+  check_usable(g);
+  spmv_stats_reset();
+  hipStream_t cs = g->compute;
+  cbg_tile shape{};
+  shape.m = A ? A->m : At->n;
+  shape.n = A ? A->n : At->m;
+  int64_t roff = 0, coff = 0;
+  int rc = tile_place(g, shape, gm, gn, &roff, &coff) ? (int)CBG_OK : (int)CBG_ERR_DIMMISMATCH;
+  if ((rc = agree(g, rc))) return rc;
+  const int64_t lm = shape.m, ln = shape.n, per = gm / g->pr;
+  const int64_t lmax = gm - (int64_t)(g->pr - 1) * per;  // the last row block is the longest
+  TileGuard own;
+  DBuf<double> dx, dy, all;
+  // 1. the tile product into lm doubles
+  rc = step([&] {
+    dx.reset(std::max<int64_t>(ln, 1));
+    dy.reset(std::max<int64_t>(lm, 1));
+    if ((At ? At->nnz : A->nnz) == 0) {  // an empty tile: id everywhere, no kernel
+      std::vector<double> id((size_t)std::max<int64_t>(lm, 1), spmv_identity(sr));
+      CBG_HIP(hipMemcpy(dy.p, id.data(), sizeof(double) * id.size(), hipMemcpyHostToDevice));
+      return;
+    }
+    if (ln) CBG_HIP(hipMemcpyAsync(dx.p, x + coff, sizeof(double) * ln, hipMemcpyHostToDevice, cs));
+    if (!At) {
+      tile_transpose(*A, own.t, cs);
+      CBG_HIP(hipStreamSynchronize(cs));
+      At = &own.t;
+    }
+    tile_spmv_device(*At, sr, dx.p, dy.p, cs);
+    CBG_HIP(hipStreamSynchronize(cs));
+    (void)spmv_stats();
+  });
+  if ((rc = agree(g, rc))) return rc;
+  // 2. the grid row's results in grid-column order
+  rc = step([&] {
+    if (g->pc == 1 || lm == 0) return;
+    all.reset((size_t)lm * g->pc);
+    allgather_device(g, COMM_ROW, dy.p, all.p, sizeof(double) * lm);
+    spmv_combine_device(dy.p, all.p, g->pc, lm, sr, cs);
+    CBG_HIP(hipStreamSynchronize(cs));
+  });
+  if ((rc = agree(g, rc))) return rc;
+  // 3. every row block to every rank
+  rc = step([&] {
+    if (g->pr == 1) {
+      if (lm) CBG_HIP(hipMemcpy(y, dy.p, sizeof(double) * lm, hipMemcpyDeviceToHost));
+      return;
+    }
+    const int64_t l1 = std::max<int64_t>(lmax, 1);
+    std::vector<double> mine((size_t)l1, 0.0), col((size_t)l1 * g->pr);
+    if (lm) CBG_HIP(hipMemcpy(mine.data(), dy.p, sizeof(double) * lm, hipMemcpyDeviceToHost));
+    allgather_bytes(g, COMM_COL, mine.data(), col.data(), sizeof(double) * l1);
+    for (int q = 0; q < g->pr; ++q) {
+      int64_t a = 0, b = 0;
+      block_span(gm, g->pr, q, a, b);
+      if (b > a) std::memcpy(y + a, col.data() + (size_t)q * l1, sizeof(double) * (b - a));
+    }
+  });
+  if ((rc = agree(g, rc))) return rc;
+  return CBG_OK;
+}
+
+// variable-length (id, value) lists of a communicator's ranks, concatenated in rank order
+static void allgather_entries(cbg_grid* g, int which, const std::vector<int64_t>& ind, const std::vector<double>& val,
+                              std::vector<int64_t>& cnt, std::vector<int64_t>& oind, std::vector<double>& oval) {
+  const int P = which == COMM_ROW ? g->pc : g->pr;
+  const int64_t mine = (int64_t)ind.size();
+  cnt.assign((size_t)P, 0);
+  allgather_i64(g, which, &mine, cnt.data(), 1);
+  const int64_t mx = std::max<int64_t>(*std::max_element(cnt.begin(), cnt.end()), 1);
+  std::vector<int64_t> pi((size_t)mx, 0), ai((size_t)mx * P);
+  std::vector<double> pv((size_t)mx, 0.0), av((size_t)mx * P);
+  std::copy(ind.begin(), ind.end(), pi.begin());
+  std::copy(val.begin(), val.end(), pv.begin());
+  allgather_bytes(g, which, pi.data(), ai.data(), sizeof(int64_t) * mx);
+  allgather_bytes(g, which, pv.data(), av.data(), sizeof(double) * mx);
+  oind.clear();
+  oval.clear();
+  for (int q = 0; q < P; ++q) {
+    oind.insert(oind.end(), ai.begin() + (size_t)q * mx, ai.begin() + (size_t)q * mx + cnt[q]);
+    oval.insert(oval.end(), av.begin() + (size_t)q * mx, av.begin() + (size_t)q * mx + cnt[q]);
+  }
+}
+
+int grid_spmspv(cbg_grid* g, const cbg_tile& A, int64_t gm, int64_t gn, int sr, const int64_t* xind, const double* xval,
+                int64_t nx, int64_t* yind, double* yval, int64_t* ny) {
+  check_usable(g);
+  spmv_stats_reset();
+  hipStream_t cs = g->compute;
+  int64_t roff = 0, coff = 0;
+  int rc = tile_place(g, A, gm, gn, &roff, &coff) ? (int)CBG_OK : (int)CBG_ERR_DIMMISMATCH;
+  if ((rc = agree(g, rc))) return rc;
+  const int64_t lm = A.m, ln = A.n;
+  std::vector<int64_t> li, ci;
+  std::vector<double> lv, cv;
+  // 1. the tile product with the column block's slice of x
+  rc = step([&] {
+    const int64_t* lo = std::lower_bound(xind, xind + nx, coff);
+    const int64_t* hi = std::lower_bound(lo, xind + nx, coff + ln);
+    std::vector<int64_t> lx(lo, hi);
+    for (auto& j : lx) j -= coff;
+    li.assign((size_t)std::max<int64_t>(lm, 1), 0);
+    lv.assign((size_t)std::max<int64_t>(lm, 1), 0.0);
+    int64_t lny = 0;
+    tile_spmspv(A, sr, lx.data(), xval + (lo - xind), (int64_t)lx.size(), li.data(), lv.data(), &lny, cs);
+    li.resize((size_t)lny);
+    lv.resize((size_t)lny);
+  });
+  if ((rc = agree(g, rc))) return rc;
+  // 2. the grid row's entries in grid-column order: stable sort by row, each row's entries folded in that order
+  rc = step([&] {
+    if (g->pc == 1) return;
+    std::vector<int64_t> cnt;
+    allgather_entries(g, COMM_ROW, li, lv, cnt, ci, cv);
+    li.assign(ci.size() + 1, 0);
+    lv.assign(cv.size() + 1, 0.0);
+    const int64_t runs = spmspv_combine(ci.data(), cv.data(), (int64_t)ci.size(), lm, sr, li.data(), lv.data(), cs);
+    li.resize((size_t)runs);
+    lv.resize((size_t)runs);
+  });
+  if ((rc = agree(g, rc))) return rc;
+  // 3. every row block's entries to every rank, as global rows
+  rc = step([&] {
+    for (auto& i : li) i += roff;
+    if (g->pr > 1) {
+      std::vector<int64_t> cnt;
+      allgather_entries(g, COMM_COL, li, lv, cnt, ci, cv);
+      li.swap(ci);
+      lv.swap(cv);
+    }
+    std::copy(li.begin(), li.end(), yind);
+    std::copy(lv.begin(), lv.end(), yval);
+    *ny = (int64_t)li.size();
+  });
+  if ((rc = agree(g, rc))) return rc;
+  return CBG_OK;
+}
+
 }  // namespace cbg
 
 extern "C" int cbg_get_unique_id(void* id) {

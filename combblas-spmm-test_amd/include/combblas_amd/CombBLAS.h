@@ -998,6 +998,84 @@ BFSResult BFS(SpParMat<IT, NT, DER>& A, IT root, int direction = CBG_BFS_AUTO, c
   return r;
 }
 
+// SpMV<SR>(A, x) with a dense vector (ParFriends.h:1922-1990, cbg_grid_spmv) on its global values
+// (FullyDistVec is not on this path): x has A.getncol() values, the same on every rank; the result has
+// A.getnrow(), the same on every rank.  SR: PlusTimesSRing<double,double> or MinPlusSRing<double,double>.
+// Any pr x pc grid.  At: the local tile's transpose (cbg_tile_transpose), or NULL: made for the call.
+template <typename SR, typename IT, typename NT, typename DER>
+std::vector<double> SpMV(SpParMat<IT, NT, DER>& A, const std::vector<double>& x, const cbg_tile* At = nullptr) {
+  if ((int64_t)x.size() != (int64_t)A.getncol()) cbg_abort_on(CBG_ERR_DIMMISMATCH, "SpMV: x has one value per column");
+  std::vector<double> y((size_t)std::max<int64_t>(A.getnrow(), 1)), xs(x);
+  if (xs.empty()) xs.push_back(0.0);
+  cbg_abort_on(cbg_grid_spmv(A.commGrid->handle(), A.spSeq->tile(), At, A.getnrow(), A.getncol(), SR::code, xs.data(),
+                             y.data()),
+               "SpMV");
+  y.resize((size_t)A.getnrow());
+  return y;
+}
+// ... and with a sparse vector (ParFriends.h:1892-1897, cbg_grid_spmspv): (global ids ascending, values) in,
+// the same out: one entry per row with a product
+template <typename SR, typename IT, typename NT, typename DER>
+void SpMV(SpParMat<IT, NT, DER>& A, const std::vector<int64_t>& xind, const std::vector<double>& xval,
+          std::vector<int64_t>& yind, std::vector<double>& yval) {
+  if (xind.size() != xval.size()) cbg_abort_on(CBG_ERR_INVALIDPARAMS, "SpMV: one value per index");
+  const size_t room = (size_t)std::max<int64_t>(A.getnrow(), 1);
+  std::vector<int64_t> xi(xind);
+  std::vector<double> xv(xval);
+  if (xi.empty()) xi.push_back(0), xv.push_back(0.0);
+  yind.assign(room, 0);
+  yval.assign(room, 0.0);
+  int64_t ny = 0;
+  cbg_abort_on(cbg_grid_spmspv(A.commGrid->handle(), A.spSeq->tile(), A.getnrow(), A.getncol(), SR::code, xi.data(),
+                               xv.data(), (int64_t)xind.size(), yind.data(), yval.data(), &ny),
+               "SpMV (sparse)");
+  yind.resize((size_t)ny);
+  yval.resize((size_t)ny);
+}
+// the stored entries of a vector file (FullyDistSpVec::ReadDistribute, FullyDistSpVec.cpp:1397-1437): the
+// same format as ReadDistributeVector below, every listed entry stored (a listed 0 too); ids ascending
+inline void ReadDistributeSpVector(const std::string& filename, std::vector<int64_t>& ind, std::vector<double>& val,
+                                   int64_t* glen = nullptr) {
+  FILE* f = std::fopen(filename.c_str(), "r");
+  if (!f) cbg_abort_on(3004, ("ReadDistribute: file " + filename + " can not be found").c_str());  // NOFILE
+  char line[1024];
+  long long m = 0, n = 0, nz = 0;
+  if (!std::fgets(line, sizeof line, f) || std::sscanf(line, "%lld %lld %lld", &m, &n, &nz) != 3)
+    cbg_abort_on(CBG_ERR_INVALIDPARAMS, "ReadDistribute: bad vector header");
+  const long long len = n == 1 ? m : n;
+  std::vector<std::pair<int64_t, double>> e;
+  for (long long k = 0; k < nz && std::fgets(line, sizeof line, f); ++k) {
+    long long i, j;
+    double v = 1.0;
+    if (std::sscanf(line, "%lld %lld %lg", &i, &j, &v) < 2) continue;
+    const long long x = (n == 1 ? i : j) - 1;
+    if (x >= 0 && x < len) e.emplace_back((int64_t)x, v);
+  }
+  std::fclose(f);
+  std::stable_sort(e.begin(), e.end(), [](const std::pair<int64_t, double>& a, const std::pair<int64_t, double>& b) {
+    return a.first < b.first;
+  });
+  ind.clear();
+  val.clear();
+  for (const auto& p : e) {
+    if (!ind.empty() && ind.back() == p.first) {  // listed twice: the last one stays
+      val.back() = p.second;
+      continue;
+    }
+    ind.push_back(p.first);
+    val.push_back(p.second);
+  }
+  if (glen) *glen = len;
+}
+// Compare.h:47-65, EPSILON of SpDefs.h:64
+inline bool ErrorTolerantEqual(double a, double b, double epsilon = 0.01) {
+  if (a == b) return true;
+  const double d = a > b ? a - b : b - a;
+  if (d < epsilon) return true;
+  const double aa = a < 0 ? -a : a, bb = b < 0 ? -b : b;
+  return d / (aa > bb ? aa : bb) < epsilon;
+}
+
 // BlockSpGEMM (BlockSpGEMM.h:14-131): C = A*B block by block, A split into br
 // row blocks and B into bc column blocks (bi = 1), each block product a
 // Mult_AnXBn_DoubleBuff

@@ -691,6 +691,71 @@ enum { CBG_BFS_MS_PUSH = 0, CBG_BFS_MS_PULL = 1, CBG_BFS_MS_UPDATE = 2, CBG_BFS_
        CBG_BFS_MS_N = 5 };
 int cbg_last_bfs_stats(int64_t* counts, int n, double* ms);
 
+/* ---------------- matrix x vector on PlusTimes and MinPlus ----------------
+ * SpMV<SR> (ParFriends.h:1860-1990, the local kernels dcsc_gespmv Friends.h:63-78 and SpMXSpV SpImpl.cpp) for
+ * SR = CBG_PLUS_TIMES or CBG_MIN_PLUS over doubles, with a dense or a sparse x.
+ *
+ * The products of row i are mul(a(i, j), x[j]) for the stored (i, j) whose j takes part, in ascending j, each
+ * rounded on its own (no fused multiply-add).  With a dense x every stored column takes part (a stored entry
+ * times x[j] = 0 is still a product); with a sparse x exactly the columns of xind.  mul of MinPlus is inf_plus
+ * (DBL_MAX if either side is DBL_MAX, else a + b), its add is b < a ? b : a.
+ * The order of a row's sum depends on the number L of its products alone: L <= 16: 16 lanes, L <= 4096:
+ * 64 lanes; lane l starts at the identity (-0.0, +inf) and folds products l, l + G, ... one after another, then
+ * the lanes are combined by the xor tree over distances 1, 2, 4, ...  A longer list is cut into chunks of 4096
+ * products (the last one shorter), each reduced as a 64-lane row, and the chunk results are folded one after
+ * another.  tests/spmv_ref.py restates it.  r_i is that sum.
+ *   dense result   y[i] = add(SR::id(), r_i) with the reference's id, 0.0 and DBL_MAX; a row without a stored
+ *                  entry gives id (ParFriends.h:1960-1968).  A row whose products are all -0.0 gives +0.0.
+ *   sparse result  one entry per row with at least one product, rows ascending, value r_i itself: a cancelled
+ *                  sum stays as a stored 0.0 and a row of -0.0 products gives -0.0 (the reference's first insert).
+ * On a grid each rank computes this on its tile and its slice of x, and the results of a grid row's ranks are
+ * combined with SR::add in grid-column order 0, 1, ...; a rank without the row contributes nothing (sparse) or
+ * id (dense).  No atomics: the same bits in every run, on every rank and on either transport.
+ * A NaN in A or x, and for MinPlus a sum whose minimum is a zero that occurs with both signs, give an
+ * unspecified result.
+ *
+ * Refusals, before any device work (collectively on a grid): CBG_ERR_INVALIDPARAMS for an unknown semiring, an
+ * xind that is unsorted, repeated or outside, a negative count, a NULL output, or A and At both NULL;
+ * CBG_ERR_DIMMISMATCH for an At that is not A's transpose shape, or a tile that is not this rank's block of
+ * gm x gn.  An empty tile answers without a kernel.
+ *
+ * y = A x, dense.  At = cbg_tile_transpose(A) or NULL (made from A for this call and freed, which waits);
+ * A may be NULL when At is given.  x: n doubles, y: m doubles; on_device != 0: both are device memory and the
+ * call is asynchronous on `stream` (the tile and the vectors must stay until it has run), else HOST. */
+int cbg_tile_spmv(const cbg_tile* A, const cbg_tile* At, int semiring, const double* x, double* y, int on_device,
+                  void* hip_stream);
+/* y = A x, sparse.  xind: nx distinct local column ids, ascending; xval: nx doubles;
+ * yind / yval: room for A->m; *ny entries, yind ascending.  HOST arrays. */
+int cbg_tile_spmspv(const cbg_tile* A, int semiring, const int64_t* xind, const double* xval, int64_t nx,
+                    int64_t* yind, double* yval, int64_t* ny);
+/* collective over any pr x pc grid (the reference's dense SpMV needs a square one); x (HOST, gn doubles) and
+ * y (HOST, gm doubles) the same on every rank, as `parents` of cbg_grid_bfs.  At_local: the local tile's
+ * transpose or NULL. */
+int cbg_grid_spmv(cbg_grid* g, const cbg_tile* A_local, const cbg_tile* At_local, int64_t gm, int64_t gn,
+                  int semiring, const double* x, double* y);
+/* x as (global ids ascending, values), the same on every rank; y likewise (room for gm) */
+int cbg_grid_spmspv(cbg_grid* g, const cbg_tile* A_local, int64_t gm, int64_t gn, int semiring, const int64_t* xind,
+                    const double* xval, int64_t nx, int64_t* yind, double* yval, int64_t* ny);
+/* bounds[0] = 16 and bounds[1] = 4096, the longest rows of the 16-lane and the wave class (4096 is also the
+ * chunk of the longer ones); bounds[2] = C, the entries of a column of x one expansion unit of the sparse
+ * product takes.  bounds[i] for i < min(n, 3); returns 3 */
+int cbg_spmv_bounds(int64_t* bounds, int n);
+/* the last product on this thread (a grid call: this rank's tile product): rows run by the 16-lane, the wave and
+ * the chunked class, chunks; sparse: units, products expanded, entries out.  counts[i] for i < min(n, CBG_SPMV_N);
+ * *ms (may be NULL): ms between two device events around the call's kernels (the sparse product's span holds
+ * its two host readbacks).  Waits for an asynchronous product.  Returns CBG_SPMV_N. */
+enum {
+  CBG_SPMV_ROWS_GROUP = 0,
+  CBG_SPMV_ROWS_WAVE = 1,
+  CBG_SPMV_ROWS_LONG = 2,
+  CBG_SPMV_CHUNKS = 3,
+  CBG_SPMV_UNITS = 4,
+  CBG_SPMV_PRODUCTS = 5,
+  CBG_SPMV_ENTRIES_OUT = 6,
+  CBG_SPMV_N = 7
+};
+int cbg_last_spmv_stats(int64_t* counts, int n, double* ms);
+
 /* p (HOST, n int64) = the stable argsort of key[i] = mix64(seed ^ (i * 0x9E3779B97F4A7C15)), i = 0..n-1
  * (mix64: the finalizer of cbg_tile_digest).  Equal keys keep index order.  Computed on the host.
  * This library's RandPerm (FullyDistVec::RandPerm as MCL.cpp:496-512 uses it): the
