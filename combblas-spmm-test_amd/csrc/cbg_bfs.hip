@@ -6,8 +6,8 @@
 // reaches.  This is the transpose of what cbg_grid_betwcent calls A.  Values are never read.
 //
 //   push   The frontier is an ascending list of local columns.  A unit is (frontier entry, chunk of at
-//          most BFS_CHUNK entries of its column), one wave each, found by a search in the scan of the
-//          units per entry: one hub column still fills the device.  Every entry does one vector
+//          most EXPAND_UNIT entries of its column), one wave each, found by a search in the scan of the
+//          units per entry (cbg_vector.h): one hub column still fills the device.  Every entry does one vector
 //          atomicMax(&cand[row], value) on the dense candidate array (-1: none).  The atomics execute at
 //          the memory side, so cand is not cached across them and needs no ordering: max is idempotent.
 //   pull   At is the tile's transpose: its column i is row i of A with the column ids ascending.  A row
@@ -23,8 +23,7 @@
 #include <algorithm>
 #include <climits>
 
-#include "cbg_device.h"
-#include "cbg_internal.h"
+#include "cbg_vector.h"
 
 namespace cbg {
 
@@ -34,20 +33,21 @@ BfsStats& bfs_stats() {
 }
 
 namespace {
-// A unit's entries: 4 trips of a wave.  A scale-20 hub column of 10^5 entries gives 400 waves, and the
-// unit's search over the frontier (20 steps) stays small against its 256 atomics.
-constexpr int BFS_CHUNK = 256;
 // The longest row one lane scans.  Its reads are not coalesced, so only rows that fit a couple of cache
 // lines of row ids stay here; the serial scan of a longer row would also hold its wave back.
 constexpr int BFS_PULL_LANE = 16;
-constexpr int WAVES = 256 / WAVE;
 
 __device__ __forceinline__ bool bit_at(const u64* __restrict__ bits, int64_t g) { return (bits[g >> 6] >> (g & 63)) & 1ull; }
 
-__global__ __launch_bounds__(256) void k_bfs_units(int64_t nf, const int32_t* __restrict__ fl,
-                                                   const int64_t* __restrict__ len, int64_t* __restrict__ nu) {
+// nu[k] = the units of column fl[k]; plen[k] (plen may be NULL) = its stored length
+__global__ __launch_bounds__(256) void k_expand_units(int64_t nf, const int32_t* __restrict__ fl,
+                                                      const int64_t* __restrict__ len, int64_t* __restrict__ plen,
+                                                      int64_t* __restrict__ nu) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k < nf) nu[k] = (len[fl[k]] + BFS_CHUNK - 1) / BFS_CHUNK;
+  if (k >= nf) return;
+  const int64_t n = len[fl[k]];
+  if (plen) plen[k] = n;
+  nu[k] = (n + EXPAND_UNIT - 1) / EXPAND_UNIT;
 }
 
 __device__ __forceinline__ void atomic_max(int32_t* p, int32_t v) { atomicMax(p, v); }
@@ -63,26 +63,13 @@ __global__ __launch_bounds__(256) void k_bfs_push(int64_t nf, const int32_t* __r
                                                   int64_t units, V* __restrict__ cand) {
   const int64_t u = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   if (u >= units) return;
-  // the unit's frontier entry: the last k with ustart[k] <= u (an entry without units shares its start
-  // with the next one and is never the last)
-  int64_t lo = 0, hi = nf;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (ustart[mid] <= u) lo = mid;
-    else hi = mid;
-  }
+  const int64_t lo = unit_owner(ustart, nf, u);  // the unit's frontier entry
   const int32_t j = fl[lo];
   const int32_t p = pos[j];
   if (p < 0) return;  // not stored: it has no unit, so this is never taken
-  const int64_t a0 = cp[p] + (u - ustart[lo]) * BFS_CHUNK, a1 = min(a0 + BFS_CHUNK, cp[p + 1]);
+  const int64_t a0 = cp[p] + (u - ustart[lo]) * EXPAND_UNIT, a1 = min(a0 + EXPAND_UNIT, cp[p + 1]);
   const V v = xv ? xv[lo] : (V)j;
   for (int64_t x = a0 + lane_id(); x < a1; x += WAVE) atomic_max(cand + ld_stream(ir + x), v);
-}
-
-template <class V>
-__global__ __launch_bounds__(256) void k_bfs_fill(V* __restrict__ d, int64_t n, V v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) d[i] = v;
 }
 
 // stat: 0 rows scanned, 1 entries read, 2 rows queued for k_bfs_pull_long
@@ -167,14 +154,9 @@ __global__ __launch_bounds__(256) void k_bfs_cand_global(const int32_t* __restri
   if (i < lm) candg[i] = cand[i] < 0 ? -1 : coff + cand[i];
 }
 
-__global__ __launch_bounds__(256) void k_bfs_cand_max(int64_t* __restrict__ candg, const int64_t* __restrict__ all, int P,
-                                                      int64_t lm) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= lm) return;
-  int64_t v = all[i];
-  for (int q = 1; q < P; ++q) v = max(v, all[(int64_t)q * lm + i]);
-  candg[i] = v;
-}
+struct MaxI64 {
+  __device__ __forceinline__ int64_t operator()(int64_t a, int64_t b) const { return max(a, b); }
+};
 
 // rowbits: wb words; the grid covers wb * 64 rows
 __global__ __launch_bounds__(256) void k_bfs_update(int64_t lm, const int64_t* __restrict__ candg,
@@ -232,7 +214,7 @@ __global__ __launch_bounds__(256) void k_bfs_front_emit(int64_t ln, const u64* _
   if (in) {
     const int64_t at = off[j >> 6] + __popcll(m & ((1ull << lane) - 1ull));
     l = len[j];
-    units = (l + BFS_CHUNK - 1) / BFS_CHUNK;
+    units = (l + EXPAND_UNIT - 1) / EXPAND_UNIT;
     fl[at] = (int32_t)j;
     nu[at] = units;
   }
@@ -246,7 +228,7 @@ __global__ __launch_bounds__(256) void k_bfs_front_emit(int64_t ln, const u64* _
 }  // namespace
 
 int bfs_bounds(int64_t* bounds, int n) {
-  const int64_t b[2] = {BFS_CHUNK, BFS_PULL_LANE};
+  const int64_t b[2] = {EXPAND_UNIT, BFS_PULL_LANE};
   for (int i = 0; bounds && i < n && i < 2; ++i) bounds[i] = b[i];
   return 2;
 }
@@ -282,8 +264,7 @@ void bfs_cand_global(const int32_t* cand, int64_t lm, int64_t coff, int64_t* can
   CBG_HIP(hipGetLastError());
 }
 void bfs_cand_max(int64_t* candg, const int64_t* all, int P, int64_t lm, hipStream_t s) {
-  if (lm > 0) hipLaunchKernelGGL(k_bfs_cand_max, dim3(nblk(lm, 256)), dim3(256), 0, s, candg, all, P, lm);
-  CBG_HIP(hipGetLastError());
+  fold_blocks(candg, all, P, lm, MaxI64{}, s);
 }
 void bfs_update(int64_t lm, const int64_t* candg, int64_t* parent, int64_t* level, int64_t lev, u64* rowbits, int64_t wb,
                 u64* count, hipStream_t s) {
@@ -312,47 +293,51 @@ void bfs_compact(const u64* bits, int64_t coff, int64_t ln, const int64_t* len, 
   CBG_HIP(hipGetLastError());
 }
 
-namespace {
-struct WaitOnThrow {  // declared after the buffers, so it runs first
-  hipStream_t s;
-  bool done = false;
-  ~WaitOnThrow() {
-    if (!done) (void)hipStreamSynchronize(s);
+void expand_plan(const int32_t* fl, int64_t nf, const int64_t* len, bool products, ExpandPlan& pl, hipStream_t s) {
+  const int64_t n1 = nf + 1;
+  pl.buf.reset((products ? 4 : 2) * n1);
+  int64_t *nu = pl.buf.p, *plen = products ? nu + 2 * n1 : nullptr;
+  pl.ustart = nu + n1, pl.pstart = products ? nu + 3 * n1 : nullptr;
+  pl.units = pl.products = 0;
+  DeferredFree df;
+  hipLaunchKernelGGL(k_expand_units, dim3(nblk(nf, 256)), dim3(256), 0, s, nf, fl, len, plen, nu);
+  exclusive_scan_i64(nu, pl.ustart, nf, s, &df);
+  CBG_HIP(hipMemcpyAsync(&pl.units, pl.ustart + nf, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  if (products) {
+    exclusive_scan_i64(plen, pl.pstart, nf, s, &df);
+    CBG_HIP(hipMemcpyAsync(&pl.products, pl.pstart + nf, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   }
-};
+  CBG_HIP(hipStreamSynchronize(s));
+  df.synced = true;
+}
 
+namespace {
 template <class V>
 void spmspv_run(const cbg_tile& A, const std::vector<int32_t>& fl_h, const int64_t* xval, V none, std::vector<V>& cand_h,
                 hipStream_t s) {
   const int64_t nf = (int64_t)fl_h.size(), m1 = std::max<int64_t>(A.m, 1), n1 = std::max<int64_t>(A.n, 1);
   DBuf<V> cand(m1), xv;
   DBuf<int32_t> pos(n1), fl(std::max<int64_t>(nf, 1));
-  DBuf<int64_t> len(n1), nu(2 * nf + 2);
-  DeferredFree df;
-  WaitOnThrow wait{s};
-  hipLaunchKernelGGL(k_bfs_fill<V>, dim3(nblk(m1, 256)), dim3(256), 0, s, cand.p, m1, none);
-  int64_t units = 0;
+  DBuf<int64_t> len(n1);
+  ExpandPlan plan;
+  WaitOnThrow wait{s};  // after the buffers
+  fill_device(cand.p, m1, none, s);
   if (nf > 0 && A.nnz > 0 && A.nzc > 0) {
-    int64_t* ustart = nu.p + nf + 1;
     tile_col_map(A, pos.p, len.p, s);
     CBG_HIP(hipMemcpyAsync(fl.p, fl_h.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, s));
     if (xval) {
       xv.reset(nf);
       CBG_HIP(hipMemcpyAsync(xv.p, xval, sizeof(V) * nf, hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(k_bfs_units, dim3(nblk(nf, 256)), dim3(256), 0, s, nf, fl.p, len.p, nu.p);
-    exclusive_scan_i64(nu.p, ustart, nf, s, &df);
-    CBG_HIP(hipMemcpyAsync(&units, ustart + nf, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CBG_HIP(hipStreamSynchronize(s));
-    push_launch<V>(A, pos.p, fl.p, xv.p, nf, ustart, units, cand.p, s);
+    expand_plan(fl.p, nf, len.p, false, plan, s);
+    push_launch<V>(A, pos.p, fl.p, xv.p, nf, plan.ustart, plan.units, cand.p, s);
   }
   cand_h.resize((size_t)m1);
   CBG_HIP(hipMemcpyAsync(cand_h.data(), cand.p, sizeof(V) * m1, hipMemcpyDeviceToHost, s));
   CBG_HIP(hipStreamSynchronize(s));
   CBG_HIP(hipGetLastError());
-  df.synced = true;
   wait.done = true;
-  bfs_stats().counts[CBG_BFS_PUSH_UNITS] += units;
+  bfs_stats().counts[CBG_BFS_PUSH_UNITS] += plan.units;
 }
 }  // namespace
 

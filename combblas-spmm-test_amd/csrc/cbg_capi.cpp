@@ -4,61 +4,7 @@
 #include <cfloat>
 #include <cstring>
 
-#include "cbg_internal.h"
-
-struct cbg_grid;
-namespace cbg {
-void rmat_tile(int scale, int ef, uint64_t userseed, int pr, int pc, int prow, int pcol, cbg_tile& out, hipStream_t s);
-void tile_digest(const cbg_tile& t, int64_t roff, int64_t coff, uint64_t* hs, uint64_t* hv, double* vsum,
-                 uint64_t* unsorted, hipStream_t s);
-bool tile_equal(const cbg_tile& a, const cbg_tile& b, double eps, hipStream_t s);
-int grid_shape(int nranks, int& rows, int& cols);
-cbg_grid* grid_create_rccl(int rank, int nranks, int rows, int cols, const void* uid);
-cbg_grid* grid_create_host(int rank, int nranks, int rows, int cols, const cbg_host_comm* hc);
-void grid_destroy(cbg_grid* g);
-void allreduce_f64(cbg_grid* g, double* v, bool max);
-void allreduce_sum_i64(cbg_grid* g, int64_t* v);
-void barrier(cbg_grid* g);
-int summa_spgemm(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr, int algo,
-                 int exec, cbg_tile& C);
-int summa_spgemm_phased(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr,
-                        int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C);
-int grid_transpose(cbg_grid* g, const cbg_tile& T, cbg_tile& out);
-int agree(cbg_grid* g, int rc);
-int grid_block_extract(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, int dim, int64_t lo, int64_t hi,
-                       cbg_tile& out);
-int grid_mcl_prune(cbg_grid* g, const cbg_tile& T, const cbg_mcl_params* p, cbg_tile& out);
-int grid_kselect(cbg_grid* g, const cbg_tile& T, const int32_t* cols, int64_t ncols, int64_t k, double* kth);
-int summa_spgemm_mcl(cbg_grid* g, const cbg_tile& A, const cbg_tile& B, int64_t A_gncol, int64_t B_gnrow, int sr,
-                     int algo, int exec, int phases, int64_t mem_gb, cbg_phase_fn fn, void* user, cbg_tile* C,
-                     const cbg_mcl_params& p);
-int grid_reduce_cols(cbg_grid* g, const cbg_tile& T, int what, double identity, double* out);
-int grid_make_col_stochastic(cbg_grid* g, cbg_tile& T);
-int grid_chaos(cbg_grid* g, const cbg_tile& T, double* chaos);
-int grid_inflate(cbg_grid* g, cbg_tile& T, double power, double* chaos);
-int grid_remove_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out, int64_t* removed);
-int grid_add_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const double* loopvals, int replace,
-                   cbg_tile& out);
-int grid_adjust_loops(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, cbg_tile& out);
-int grid_connected_components(cbg_grid* g, const cbg_tile& T, int64_t gn, int64_t* labels, int64_t* ncomp);
-int grid_hipmcl(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P, cbg_hipmcl_iter_fn fn,
-                void* user, cbg_tile* final_local, int64_t* labels, int64_t* nclusters, int64_t* iterations);
-int grid_spref(cbg_grid* g, const cbg_tile& T, int64_t gm, int64_t gn, const int64_t* ri, int64_t nri,
-               const int64_t* ci, int64_t nci, cbg_tile& out);
-int grid_betwcent(cbg_grid* g, const cbg_tile& A, const cbg_tile* AT, int64_t gn, const int64_t* roots, int64_t nroots,
-                  const cbg_betwcent_params& P, cbg_betwcent_level_fn fn, void* user, double* bc);
-int grid_bfs(cbg_grid* g, const cbg_tile& A, int64_t gn, int64_t root, const cbg_bfs_params& P, cbg_bfs_level_fn fn,
-             void* user, int64_t* parents, int64_t* levels);
-int grid_spmv(cbg_grid* g, const cbg_tile* A, const cbg_tile* At, int64_t gm, int64_t gn, int sr, const double* x,
-              double* y);
-int grid_spmspv(cbg_grid* g, const cbg_tile& A, int64_t gm, int64_t gn, int sr, const int64_t* xind, const double* xval,
-                int64_t nx, int64_t* yind, double* yval, int64_t* ny);
-void rand_perm(int64_t n, uint64_t seed, int64_t* p);
-int grid_nonisolated(cbg_grid* g, const cbg_tile& A, int64_t gn, std::vector<int64_t>& ids);
-int grid_hipmcl_prepared(cbg_grid* g, const cbg_tile& A, int64_t gn, const cbg_hipmcl_params& P,
-                         const cbg_hipmcl_prep& prep, cbg_hipmcl_iter_fn fn, void* user, cbg_tile* final_local,
-                         int64_t* labels, int64_t* nclusters, int64_t* iterations, int64_t* work_ids, int64_t* n_work);
-}  // namespace cbg
+#include "cbg_grid.h"
 
 namespace {
 thread_local std::string g_err;
@@ -812,7 +758,6 @@ int cbg_grid_hipmcl(cbg_grid* g, const cbg_tile* A_local, int64_t gn, const cbg_
 }
 
 // ---------------- sparse indexing ----------------
-int cbg_grid_info(const cbg_grid* g, int* rank, int* nranks, int* rows, int* cols, int* prow, int* pcol);
 static int index_args(const char* what, const int64_t* idx, int64_t n, int64_t ext) {
   if (!idx) return CBG_OK;
   if (n < 0) return fail(CBG_ERR_INVALIDPARAMS, std::string("a negative number of ") + what + " indices");
@@ -841,16 +786,15 @@ int cbg_grid_spref(cbg_grid* g, const cbg_tile* local, int64_t gm, int64_t gn, c
   int arg = check_tile(local, true, "tile");
   if (!arg && !out) arg = fail(CBG_ERR_INVALIDPARAMS, "out is NULL");
   if (!arg && (gm < 0 || gn < 0)) arg = fail(CBG_ERR_INVALIDPARAMS, "gm or gn is negative");
-  if (!arg) {  // the tile's place (SpParMat::Owner): blocks of ext / np, the last one longer
+  if (!arg) {  // the tile's place (Blocks)
     int pr = 1, pc = 1, prow = 0, pcol = 0;
     cbg_grid_info(g, nullptr, nullptr, &pr, &pc, &prow, &pcol);
-    const int64_t m = prow == pr - 1 ? gm - (int64_t)prow * (gm / pr) : gm / pr;
-    const int64_t n = pcol == pc - 1 ? gn - (int64_t)pcol * (gn / pc) : gn / pc;
-    if (local->m != m || local->n != n) arg = fail(CBG_ERR_INVALIDPARAMS, "gm x gn does not fit the tile's place in the grid");
+    if (local->m != cbg::Blocks{gm, pr}.len(prow) || local->n != cbg::Blocks{gn, pc}.len(pcol))
+      arg = fail(CBG_ERR_INVALIDPARAMS, "gm x gn does not fit the tile's place in the grid");
     const int64_t nm = ri ? nri : gm, nn = ci ? nci : gn;
     if (!arg) arg = index_args("row", ri, nri, gm);
     if (!arg) arg = index_args("column", ci, nci, gn);
-    if (!arg && (nm - (int64_t)(pr - 1) * (nm / pr) >= INT32_MAX || nn - (int64_t)(pc - 1) * (nn / pc) >= INT32_MAX))
+    if (!arg && (cbg::Blocks{nm, pr}.longest() >= INT32_MAX || cbg::Blocks{nn, pc}.longest() >= INT32_MAX))
       arg = fail(CBG_ERR_NOTSUPPORTED, "a new local block has 2^31 or more rows or columns");
   }
   // every check above precedes any device work; the code is agreed over the grid
@@ -1211,7 +1155,5 @@ int cbg_merge_stats(int64_t* entries_in, int64_t* entries_out, double* ms) {
   if (ms) *ms = m.ms;
   return CBG_OK;
 }
-
-int cbg_grid_info(const cbg_grid* g, int* rank, int* nranks, int* rows, int* cols, int* prow, int* pcol);
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "cbg_rebuild.h"
+#include "cbg_vector.h"
 
 namespace cbg {
 
@@ -41,7 +42,6 @@ constexpr int EWISE_CHUNK = 512;
 // this long is a b 2.5 times denser than a over the chunk's rows; denser still goes to class 2.
 constexpr int EWISE_LDS_RANGE = 1280;
 constexpr int WORDS = EWISE_CHUNK / WAVE;  // ballot words per unit
-constexpr int WAVES = 256 / WAVE;
 
 struct Ew {
   int64_t anzc, bnzc;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void k_ewise_count(Ew p) {
     if (lane == 0) p.cnt[u] = 0;
     return;
   }
-  // the unit's column: the last i with ustart[i] <= u
+  // the unit's column: the last i with ustart[i] <= u (written out: unit_owner costs this kernel 6 SGPRs)
   int64_t lo = 0, hi = p.anzc;
   while (hi - lo > 1) {
     const int64_t mid = lo + (hi - lo) / 2;
@@ -229,13 +229,7 @@ void tile_ewise(const cbg_tile& a, const cbg_tile* b, int op, cbg_tile& out, hip
   DBuf<u64> mask(umax * WORDS);
   DBuf<int64_t> stat(5);
   DeferredFree df;
-  struct WaitOnThrow {  // declared last, so it runs first: before the output and the buffers go
-    hipStream_t s;
-    bool done = false;
-    ~WaitOnThrow() {
-      if (!done) (void)hipStreamSynchronize(s);
-    }
-  } wait{s};
+  WaitOnThrow wait{s};  // declared last, so it runs first: before the output and the buffers go
   int64_t *nu = cols.p, *ustart = cols.p + (nzc + 1), *coloff = cols.p + 2 * (nzc + 1);
   int64_t* off = units.p + 3 * umax;
   Ew p{};
@@ -313,10 +307,6 @@ __global__ __launch_bounds__(256) void k_dense_tile(int64_t nzc, const int64_t* 
     else val[q] *= col[ir[q]];
   }
 }
-__global__ __launch_bounds__(256) void k_dense_fill(double* __restrict__ d, int64_t n, double v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) d[i] = v;
-}
 // out[i] = bcu(i, 0) + bcu(i, 1) + ... in that order; consecutive lanes read consecutive rows
 __global__ __launch_bounds__(256) void k_dense_row_sums(const double* __restrict__ bcu, int64_t lm, int64_t ln,
                                                         double* __restrict__ out) {
@@ -328,10 +318,7 @@ __global__ __launch_bounds__(256) void k_dense_row_sums(const double* __restrict
 }
 }  // namespace
 
-void dense_fill(double* d, int64_t n, double v, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_dense_fill, dim3(nblk(n, 256)), dim3(256), 0, s, d, n, v);
-  CBG_HIP(hipGetLastError());
-}
+void dense_fill(double* d, int64_t n, double v, hipStream_t s) { fill_device(d, n, v, s); }
 void dense_scale_tile(cbg_tile& t, const double* bcu, int64_t lm, hipStream_t s) {
   if (t.nzc > 0)
     hipLaunchKernelGGL(k_dense_tile<false>, dim3(nblk(t.nzc * WAVE, 256)), dim3(256), 0, s, t.nzc, t.cp, t.jc, t.ir,

@@ -186,6 +186,16 @@ struct DeferredFree {
   }
 };
 
+// A throw out of a frame with kernels running on s waits for them first.  Declare it AFTER every buffer, tile
+// guard and DeferredFree they use (destructors run in reverse order); set done after the frame's own last sync.
+struct WaitOnThrow {
+  hipStream_t s;
+  bool done = false;
+  ~WaitOnThrow() {
+    if (!done) (void)hipStreamSynchronize(s);
+  }
+};
+
 // blocks of `per` items that cover n items; at least one (a grid of 0 blocks is refused)
 inline unsigned nblk(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
 // kernels that take more than 64 KiB of dynamic LDS have to say so
@@ -267,7 +277,6 @@ int local_slab_caps(int out[4]);
 // device exclusive scan of n int64 values -> out[0..n], returns nothing (total at out[n]).
 // df: the scan's temporaries are released with df (no host synchronization);
 // without it the scan synchronizes the stream before returning them.
-struct DeferredFree;
 void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t s, DeferredFree* df = nullptr);
 void exclusive_scan_i32_to_i64(const int32_t* in, int64_t* out, int64_t n, hipStream_t s, DeferredFree* df = nullptr);
 
@@ -336,6 +345,10 @@ void tile_concat_cols(const std::vector<cbg_tile>& parts, const std::vector<int6
 void tile_concat_rows(const std::vector<cbg_tile>& parts, const std::vector<int64_t>& row_off, int64_t m,
                       int64_t n, cbg_tile& out, hipStream_t s);
 bool tile_equal(const cbg_tile& a, const cbg_tile& b, double eps, hipStream_t s);
+void tile_digest(const cbg_tile& t, int64_t roff, int64_t coff, uint64_t* hs, uint64_t* hv, double* vsum,
+                 uint64_t* unsorted, hipStream_t s);
+// this rank's tile of the R-MAT test matrix (cbg_rmat.hip)
+void rmat_tile(int scale, int ef, uint64_t userseed, int pr, int pc, int prow, int pcol, cbg_tile& out, hipStream_t s);
 // phase planning: dim 0 = nonzeros per column (length n), 1 = per row (length m),
 // into the device array d zero-padded to `padded` entries (stream synchronized)
 void tile_counts_device(const cbg_tile& t, int dim, int32_t* d, int64_t padded, hipStream_t s);
@@ -506,7 +519,6 @@ SpmvStats& spmv_stats();  // the calling thread's, summed since the last reset; 
 void spmv_stats_reset();
 int spmv_bounds(int64_t* bounds, int n);
 double spmv_identity(int sr);  // the reference's SR::id(): 0.0, DBL_MAX
-void spmv_fill_device(double* y, int64_t n, double v, hipStream_t s);
 // y (device, At.n) = A x with At = A's transpose and x (device, At.m): queued on s, nothing waits.  The
 // call's temporaries return to the pool when the thread's next product starts or its statistics are read.
 void tile_spmv_device(const cbg_tile& At, int sr, const double* x, double* y, hipStream_t s);

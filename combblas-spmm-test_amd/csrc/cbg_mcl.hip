@@ -4,7 +4,7 @@
 // column moments (sum, sum of squares, max, count in one pass), the column
 // scaling, the fused inflation pass, loops on the diagonal and the label
 // kernels of the connected components.  The grid-level logic (combining the
-// ranks of a grid column, the world's label vector) is in cbg_summa.cpp.
+// ranks of a grid column, the world's label vector) is in cbg_grid_algos.cpp.
 //
 // Sum order: exactly k_col_stats' (cbg_prune.hip).  Columns of <= 16 entries one
 // entry per lane of a 16-lane group, up to 4096 entries lane-strided partials

@@ -11,6 +11,7 @@
 #include <tuple>
 
 #include "cbg_rebuild.h"
+#include "cbg_vector.h"
 
 namespace cbg {
 
@@ -36,11 +37,6 @@ __device__ inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
 __device__ inline double val_of(u64 k) {
   const u64 u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)u);
-}
-
-__global__ void k_fill_f64(double* p, int64_t n, double v) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
 }
 
 // ---------------------------------------------------------------------------
@@ -745,7 +741,7 @@ int mcl_prune_piece(const ColComm& cc, const cbg_tile& T, const cbg_mcl_params& 
     cnt0.reset(n), cnt1.reset(n), all.reset(n), off.reset(n + 1);
     pos.reset(n), inR.reset(n), inS.reset(n), f2.reset(n), list.reset(n);
     if (cc.P > 1) pack.reset(3 * n), packs.reset((size_t)3 * n * cc.P);
-    hipLaunchKernelGGL(k_fill_f64, dim3(nblk(n, 256)), dim3(256), 0, s, thr.p, n, h);
+    fill_device(thr.p, n, h, s);
     tile_col_map(T, pos.p, all.p, s);
   });
   pend = stats(pend, 1, cnt0.p, sum0.p);

@@ -147,17 +147,10 @@ void tile_from_columns(int64_t m, int64_t n, int64_t nslots, const int32_t* ids,
     tile_alloc_device(out, m, n, 0, 0);
     return;
   }
-  struct WaitOnThrow {  // declared last, so it runs first: before the output and the buffers go
-    hipStream_t s;
-    bool done = false;
-    ~WaitOnThrow() {
-      if (!done) (void)hipStreamSynchronize(s);
-    }
-  };
   TileGuard o;
   DBuf<int64_t> buf;  // off[0 .. nslots] | pos[0 .. nslots] | the three words read back
   DeferredFree df;
-  WaitOnThrow wait{s};
+  WaitOnThrow wait{s};  // declared last, so it runs first: before the output and the buffers go
   buf.reset(2 * (nslots + 1) + 3);
   int64_t *off = buf.p, *pos = buf.p + nslots + 1, *words = buf.p + 2 * (nslots + 1);
   exclusive_scan_i64(len, off, nslots, s, &df);

@@ -17,7 +17,7 @@
 //           others; one scan of the classes queues the rows of up to 4096 entries for a wave each and
 //           gives the unit list (row, chunk) of the longer ones.  Each lane loads At.ir (4 B) and At.val (8 B) coalesced and gathers
 //           x[ir].  y is filled with SR::id() first, and a stored row writes add(SR::id(), r).
-//   sparse  x's columns go through A's column map; a unit is (column of x, chunk of at most SPMV_UNIT of
+//   sparse  x's columns go through A's column map; a unit is (column of x, chunk of at most EXPAND_UNIT of
 //           its entries), one wave each, and writes key = row, value = mul(a, x[j]) at the column's
 //           product offset: the products in ascending (j, i) order.  A stable radix sort by row keeps the
 //           products of a row in ascending j; the run heads give the segments, which the same three
@@ -26,16 +26,13 @@
 #include <cfloat>
 #include <cstring>
 
-#include "cbg_device.h"
-#include "cbg_internal.h"
+#include "cbg_vector.h"
 
 namespace cbg {
 
 namespace {
 constexpr int SPMV_GROUP = 16;     // the longest row of a 16-lane group
 constexpr int SPMV_WAVE = 4096;    // the longest row of one wave, and the chunk of the longer ones
-constexpr int SPMV_UNIT = 256;     // entries of a column of x one expansion unit takes (the BFS push's)
-constexpr int WAVES = 256 / WAVE;
 constexpr int GROUPS = 256 / SPMV_GROUP;
 
 // add(SR::id(), r) with the reference's id (0.0, DBL_MAX): what the dense product stores
@@ -158,13 +155,8 @@ __global__ __launch_bounds__(256) void k_spmv_chunk(S src, const int64_t* __rest
   const int lane = lane_id();
   const int64_t w0 = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   for (int64_t u = w0; u < units; u += (int64_t)gridDim.x * WAVES) {
-    // the unit's row: the last p whose start is <= u (a row without units shares its start with the next one)
-    int64_t lo = 0, hi = src.nrows;
-    while (hi - lo > 1) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if ((pre[mid] & CHUNK_MASK) <= u) lo = mid;
-      else hi = mid;
-    }
+    // the unit's row: the starts are the low words of pre
+    const int64_t lo = unit_owner(src.nrows, u, [&](int64_t p) { return pre[p] & CHUNK_MASK; });
     const int64_t k0 = src.begin(lo) + (u - (pre[lo] & CHUNK_MASK)) * SPMV_WAVE, k1 = min(k0 + SPMV_WAVE, src.end(lo));
     const double r = lanes_reduce<SR, WAVE>(src, k0, k1, lane);
     if (lane == 0) partial[u] = r;
@@ -184,22 +176,7 @@ __global__ __launch_bounds__(256) void k_spmv_long_fold(S src, const int64_t* __
   src.out(p, acc);
 }
 
-__global__ __launch_bounds__(256) void k_spmv_fill(double* __restrict__ d, int64_t n, double v) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) d[i] = v;
-}
-
-// ---- the sparse product's expansion ----
-// plen[k] = the stored length of x's k-th column, nu[k] = its units
-__global__ __launch_bounds__(256) void k_spmspv_count(int64_t nx, const int32_t* __restrict__ fl, const int64_t* __restrict__ len,
-                                                      int64_t* __restrict__ plen, int64_t* __restrict__ nu) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= nx) return;
-  const int64_t n = len[fl[k]];
-  plen[k] = n;
-  nu[k] = (n + SPMV_UNIT - 1) / SPMV_UNIT;
-}
-
+// ---- the sparse product's expansion (its plan: expand_plan, cbg_vector.h) ----
 // one wave per unit
 template <int SR>
 __global__ __launch_bounds__(256) void k_spmspv_expand(int64_t nx, const int32_t* __restrict__ fl, const double* __restrict__ xv,
@@ -209,16 +186,11 @@ __global__ __launch_bounds__(256) void k_spmspv_expand(int64_t nx, const int32_t
                                                        int64_t units, uint32_t* __restrict__ key, double* __restrict__ pv) {
   const int64_t u = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   if (u >= units) return;
-  int64_t lo = 0, hi = nx;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (ustart[mid] <= u) lo = mid;
-    else hi = mid;
-  }
+  const int64_t lo = unit_owner(ustart, nx, u);  // the unit's entry of x
   const int32_t p = pos[fl[lo]];
   if (p < 0) return;  // not stored: it has no unit, so this is never taken
-  const int64_t off = (u - ustart[lo]) * SPMV_UNIT;
-  const int64_t a0 = cp[p] + off, a1 = min(a0 + SPMV_UNIT, cp[p + 1]), o0 = pstart[lo] + off;
+  const int64_t off = (u - ustart[lo]) * EXPAND_UNIT;
+  const int64_t a0 = cp[p] + off, a1 = min(a0 + EXPAND_UNIT, cp[p + 1]), o0 = pstart[lo] + off;
   const double xj = xv[lo];
   for (int64_t t = lane_id(); a0 + t < a1; t += WAVE) {
     key[o0 + t] = (uint32_t)ld_stream(ir + a0 + t);
@@ -238,22 +210,9 @@ __global__ __launch_bounds__(256) void k_spmspv_starts(const uint32_t* __restric
   if (i == n || i == 0 || key[i] != key[i - 1]) start[seg[i]] = i;
 }
 
-// the ranks' dense results of a grid row in rank order: all = P blocks of lm
 template <int SR>
-__global__ __launch_bounds__(256) void k_spmv_combine(double* __restrict__ y, const double* __restrict__ all, int P, int64_t lm) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= lm) return;
-  double v = all[i];
-  for (int q = 1; q < P; ++q) v = Sem<SR>::add(v, all[(int64_t)q * lm + i]);
-  y[i] = v;
-}
-
-struct WaitOnThrow {
-  hipStream_t s;
-  bool done = false;
-  ~WaitOnThrow() {
-    if (!done) (void)hipStreamSynchronize(s);
-  }
+struct SemAdd {
+  __device__ __forceinline__ double operator()(double a, double b) const { return Sem<SR>::add(a, b); }
 };
 
 // the calling thread's state between an asynchronous product and the reading of its statistics
@@ -371,22 +330,17 @@ void spmv_stats_reset() {
 }
 
 int spmv_bounds(int64_t* bounds, int n) {
-  const int64_t b[3] = {SPMV_GROUP, SPMV_WAVE, SPMV_UNIT};
+  const int64_t b[3] = {SPMV_GROUP, SPMV_WAVE, EXPAND_UNIT};
   for (int i = 0; bounds && i < n && i < 3; ++i) bounds[i] = b[i];
   return 3;
 }
 
 double spmv_identity(int sr) { return sr == CBG_MIN_PLUS ? DBL_MAX : 0.0; }
 
-void spmv_fill_device(double* y, int64_t n, double v, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_spmv_fill, dim3(nblk(n, 256)), dim3(256), 0, s, y, n, v);
-  CBG_HIP(hipGetLastError());
-}
-
 // y (device, At.n doubles) = A x with x (device, At.m doubles); queued on s, nothing waits
 void tile_spmv_device(const cbg_tile& At, int sr, const double* x, double* y, hipStream_t s) {
   timed(s, [&](u64* stat, Pending& pd) {
-    spmv_fill_device(y, At.n, spmv_identity(sr), s);
+    fill_device(y, At.n, spmv_identity(sr), s);
     if (At.nnz <= 0 || At.nzc <= 0) return;
     if (sr == CBG_MIN_PLUS)
       reduce_rows<1>(DenseRows<1>{At.nzc, At.cp, At.jc, At.ir, At.val, x, y}, At.nnz, stat, pd, s);
@@ -396,10 +350,8 @@ void tile_spmv_device(const cbg_tile& At, int sr, const double* x, double* y, hi
 }
 
 void spmv_combine_device(double* y, const double* all, int P, int64_t lm, int sr, hipStream_t s) {
-  if (lm <= 0) return;
-  if (sr == CBG_MIN_PLUS) hipLaunchKernelGGL(k_spmv_combine<1>, dim3(nblk(lm, 256)), dim3(256), 0, s, y, all, P, lm);
-  else hipLaunchKernelGGL(k_spmv_combine<0>, dim3(nblk(lm, 256)), dim3(256), 0, s, y, all, P, lm);
-  CBG_HIP(hipGetLastError());
+  if (sr == CBG_MIN_PLUS) fold_blocks(y, all, P, lm, SemAdd<1>{}, s);
+  else fold_blocks(y, all, P, lm, SemAdd<0>{}, s);
 }
 
 // the sparse product: host vectors in and out; synchronizes s
@@ -411,10 +363,10 @@ void tile_spmspv(const cbg_tile& A, int sr, const int64_t* xind, const double* x
   for (int64_t k = 0; k < nx; ++k) fl_h[k] = (int32_t)xind[k];
   const int64_t n1 = std::max<int64_t>(A.n, 1);
   DBuf<int32_t> pos(n1), fl(nx);
-  DBuf<int64_t> len(n1), cnt(2 * nx + 2), off(2 * nx + 4);
+  DBuf<int64_t> len(n1);
   DBuf<double> xv(nx);
-  int64_t *plen = cnt.p, *nu = cnt.p + nx + 1, *pstart = off.p, *ustart = off.p + nx + 2;
-  int64_t nseg = 0, units = 0, products = 0;
+  ExpandPlan plan;
+  int64_t nseg = 0;
   std::vector<uint32_t> yi;
   bool ran = false;
   timed(s, [&](u64* stat, Pending& pd) {
@@ -422,18 +374,13 @@ void tile_spmspv(const cbg_tile& A, int sr, const int64_t* xind, const double* x
     DBuf<double> pv, ov;
     DBuf<int32_t> head;
     DBuf<int64_t> seg, start;
-    DeferredFree df, df2;
+    DeferredFree df2;
     WaitOnThrow wait{s};  // declared after the buffers, so it runs first
     tile_col_map(A, pos.p, len.p, s);
     CBG_HIP(hipMemcpyAsync(fl.p, fl_h.data(), sizeof(int32_t) * nx, hipMemcpyHostToDevice, s));
     CBG_HIP(hipMemcpyAsync(xv.p, xval, sizeof(double) * nx, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_spmspv_count, dim3(nblk(nx, 256)), dim3(256), 0, s, nx, fl.p, len.p, plen, nu);
-    exclusive_scan_i64(plen, pstart, nx, s, &df);
-    exclusive_scan_i64(nu, ustart, nx, s, &df);
-    CBG_HIP(hipMemcpyAsync(&products, pstart + nx, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CBG_HIP(hipMemcpyAsync(&units, ustart + nx, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CBG_HIP(hipStreamSynchronize(s));
-    df.synced = true;
+    expand_plan(fl.p, nx, len.p, true, plan, s);
+    const int64_t products = plan.products;
     if (products <= 0) {
       wait.done = true;
       return;
@@ -441,11 +388,11 @@ void tile_spmspv(const cbg_tile& A, int sr, const int64_t* xind, const double* x
     key.reset(products);
     pv.reset(products);
     if (sr == CBG_MIN_PLUS)
-      hipLaunchKernelGGL(k_spmspv_expand<1>, dim3(nblk(units, WAVES)), dim3(256), 0, s, nx, fl.p, xv.p, pos.p, A.cp, A.ir,
-                         A.val, ustart, pstart, units, key.p, pv.p);
+      hipLaunchKernelGGL(k_spmspv_expand<1>, dim3(nblk(plan.units, WAVES)), dim3(256), 0, s, nx, fl.p, xv.p, pos.p, A.cp, A.ir,
+                         A.val, plan.ustart, plan.pstart, plan.units, key.p, pv.p);
     else
-      hipLaunchKernelGGL(k_spmspv_expand<0>, dim3(nblk(units, WAVES)), dim3(256), 0, s, nx, fl.p, xv.p, pos.p, A.cp, A.ir,
-                         A.val, ustart, pstart, units, key.p, pv.p);
+      hipLaunchKernelGGL(k_spmspv_expand<0>, dim3(nblk(plan.units, WAVES)), dim3(256), 0, s, nx, fl.p, xv.p, pos.p, A.cp, A.ir,
+                         A.val, plan.ustart, plan.pstart, plan.units, key.p, pv.p);
     CBG_HIP(hipGetLastError());
     radix_sort_pairs<uint32_t>(key, pv, products, low_bits(A.m - 1), s, &df2);
     head.reset(products + 1);
@@ -472,8 +419,8 @@ void tile_spmspv(const cbg_tile& A, int sr, const int64_t* xind, const double* x
   });
   CBG_HIP(hipStreamSynchronize(s));
   SpmvStats& st = spmv_stats();
-  st.counts[CBG_SPMV_UNITS] += units;
-  st.counts[CBG_SPMV_PRODUCTS] += products;
+  st.counts[CBG_SPMV_UNITS] += plan.units;
+  st.counts[CBG_SPMV_PRODUCTS] += plan.products;
   if (!ran) return;
   for (int64_t k = 0; k < nseg; ++k) yind[k] = yi[k];
   *ny = nseg;

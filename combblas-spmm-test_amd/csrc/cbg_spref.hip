@@ -17,7 +17,7 @@
 //                 ones together through radix_sort_pairs on (column, row) keys.
 //                 Skipped when ri is strictly increasing: rows stay ascending.
 //
-// The grid-level logic (who broadcasts what, the agreements) is in cbg_summa.cpp.
+// The grid-level logic (who broadcasts what, the agreements) is in cbg_grid_algos.cpp.
 #include <algorithm>
 #include <chrono>
 #include <cstring>

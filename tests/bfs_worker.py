@@ -9,7 +9,8 @@ first root in one forced direction (top-down on grids of one row, bottom-up else
 transpose handed over on 2 x 2).  parents have to be the fixture's bits and levels the
 restatement's, identical on all ranks (the bits are allgathered); the steps every rank's callback
 sees and the grid-independent stats are the restatement's.  A root outside the matrix is refused
-with INVALIDPARAMS on every rank.  Prints BFSOK per rank.
+with INVALIDPARAMS on every rank.  Over the host transport every root of a path of 3 and of 5 vertices
+(row blocks of 1 | 2 and 2 | 3) has to give valid parents and the restatement's levels.  Prints BFSOK per rank.
 """
 import os
 import sys
@@ -30,6 +31,13 @@ def load_case(name):
     z = np.load(os.path.join(HERE, "golden", f"bfs_{name}.npz"))
     n = int(z["n"])
     return z, hr.from_coo(n, n, z["row"], z["col"], np.ones(len(z["row"])))
+
+
+def tiny_case(gn):
+    """the undirected path 0 - 1 - ... - gn - 1: every vertex is reached from every root, the last
+    (longer) block included"""
+    v = np.arange(gn - 1)
+    return hr.from_coo(gn, gn, np.concatenate([v, v + 1]), np.concatenate([v + 1, v]), np.ones(2 * (gn - 1)))
 
 
 def main():
@@ -78,6 +86,17 @@ def main():
                 raise AssertionError("root %d was taken" % bad)
             except cbg.CbgError as e:
                 assert e.code == cbg.INVALIDPARAMS, e
+    if mode == "gpu":
+        for gn in (3, 5):  # uneven blocks through the gather of the row blocks: 1 | 2 and 2 | 3 vertices
+            a = tiny_case(gn)
+            A = cbg.SpParMat.from_global(grid, a)
+            for root in range(gn):
+                want = bfs_ref.bfs(a, root)
+                parents, levels = cbg.BFS(A, root)
+                assert bfs_ref.validate(a, root, parents, levels) is None, (rank, gn, root, parents, levels)
+                assert np.array_equal(levels, want["levels"]), (rank, gn, root, levels)
+                mine = parents.tobytes() + levels.tobytes()
+                assert hc.allgather(0, mine) == mine * world, (rank, gn, root)
     grid.destroy()
     hc.allgather(0, b"x")
     print("BFSOK", flush=True)

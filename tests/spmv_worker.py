@@ -9,7 +9,8 @@ Every rank runs cbg.SpMV and cbg.SpMV_sparse under both semirings on the `rmat` 
 (tests/golden/spmv_*.npz) and on the `split` case, whose rows have (16, 17), (4096, 4097), (0, 30) and
 (30, 0) entries left and right of the column cut.  The results have to be spmv_ref's bits with the
 grid's column cut, identical on all ranks (the bits are allgathered); on `dyadic` they are the
-reference's own 1-rank bits.  A tile handed to a grid of another shape is refused with DIMMISMATCH
+reference's own 1-rank bits.  Over the host transport the dense product also runs on full 3 x 3 and 5 x 5
+matrices (blocks of 1 and 2, the last one longer) and on a row whose sum depends on the fold order.  A tile handed to a grid of another shape is refused with DIMMISMATCH
 on every rank.  Prints SPMVOK per rank.
 """
 import os
@@ -61,6 +62,27 @@ def split_case(n=8400):
         val = cr.pattern_values(rng, "wide", len(rows))
         _cache["split"] = hr.from_coo(r + 1, n, rows, cols, val), rng.uniform(-1.0, 1.0, n)
     return _cache["split"]
+
+
+def tiny_case(gn):
+    """a full gn x gn matrix and x of dyadic values (every sum exact): on two ranks a side the blocks are
+    gn // 2 long and the last one longer, none empty"""
+    key = ("tiny", gn)
+    if key not in _cache:
+        rng = np.random.default_rng(gn)
+        row, col = np.divmod(np.arange(gn * gn), gn)
+        val = rng.integers(1, 64, gn * gn) / 8.0 * rng.choice([-1.0, 1.0], gn * gn)
+        _cache[key] = hr.from_coo(gn, gn, row, col, val), rng.integers(-32, 33, gn) / 4.0
+    return _cache[key]
+
+
+def cancel_case():
+    """row 0 holds 1e16 left of the column cut n // 2 and -1e16, 1.0 right of it: its PlusTimes sum depends
+    on the order (one rank: (1e16 - 1e16) + 1.0), and the grid's is the ranks' partial sums folded in rank order"""
+    if "cancel" not in _cache:
+        t = hr.from_coo(2, 4, [0, 0, 0, 1], [0, 2, 3, 1], [1e16, -1e16, 1.0, 3.0])
+        _cache["cancel"] = t, np.ones(4)
+    return _cache["cancel"]
 
 
 def main():
@@ -116,6 +138,15 @@ def main():
     t, x = split_case()
     for s, sr in SEMIRINGS:
         A = check("split", s, sr, t, x, dict(all=np.arange(t["n"]), even=np.arange(0, t["n"], 2)))
+    if mode == "gpu":
+        for gn in (3, 5):  # uneven blocks through the gather of the row blocks
+            tt, tx = tiny_case(gn)
+            for s, sr in SEMIRINGS:
+                check("tiny%d" % gn, s, sr, tt, tx, {})
+        tc, cx = cancel_case()
+        check("cancel", "pt", sv.PLUS_TIMES, tc, cx, {})
+        # 1e16 + (-1e16 + 1.0): the 1.0 is lost in the right rank's partial sum, and kept without the cut
+        assert sv.spmv(tc, cx, sv.PLUS_TIMES, [2])[0] == 0.0 and sv.spmv(tc, cx, sv.PLUS_TIMES)[0] == 1.0
     if world > 1:  # the tile is not the block of a matrix one row and one column longer
         try:
             cbg.SpMV(cbg.SpParMat(A.tile, grid, t["m"] + pr, t["n"] + pc), np.zeros(t["n"] + pc))

@@ -1,4 +1,4 @@
-"""cbg_grid_betwcent (csrc/cbg_summa.cpp, kernels in csrc/cbg_ewise.hip) against the fixtures of
+"""cbg_grid_betwcent (csrc/cbg_grid_algos.cpp, kernels in csrc/cbg_ewise.hip) against the fixtures of
 tests/golden/make_betwcent_golden.py: the reference's own BetwCent agrees with the exact
 rational Brandes of tests/betwcent_ref.py there, and the device has to agree with the exact
 values within

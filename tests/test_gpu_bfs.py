@@ -1,5 +1,5 @@
 """cbg_grid_bfs, cbg_tile_spmspv_max and cbg_tile_pull_max (csrc/cbg_bfs.hip, the loop in
-csrc/cbg_summa.cpp) against the fixtures of tests/golden/make_bfs_golden.py (the reference's own
+csrc/cbg_grid_algos.cpp) against the fixtures of tests/golden/make_bfs_golden.py (the reference's own
 top-down loop) and the restatement tests/bfs_ref.py.  max is exact and order-free, so everything is
 compared by bits: parents, levels, the steps the callback sees, the direction string, the counts."""
 import ctypes

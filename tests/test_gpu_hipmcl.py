@@ -1,4 +1,4 @@
-"""The HipMCL iteration on device (csrc/cbg_mcl.hip, the loop in csrc/cbg_summa.cpp)
+"""The HipMCL iteration on device (csrc/cbg_mcl.hip, the loop in csrc/cbg_grid_algos.cpp)
 against the NumPy restatement (tests/hipmcl_ref.py).  Where the inputs' sums are exact
 (dyadic values) results are compared by bits; on inexact values the column sums, moments
 and the inflation are compared by bits with the order-exact restatement (tests/colsum_ref.py,

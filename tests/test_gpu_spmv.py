@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import bfs_ref
 import colsum_ref as cr
 import hipmcl_ref as hr
 import spmv_ref as sv
@@ -175,6 +176,34 @@ def test_sparse_vector_shapes(cbg, s, sr):
         assert st["products"] == int(lens.sum()) and st["units"] == int((-(-lens // C)).sum()), what
         assert st["entries_out"] == len(got[0])
     assert len(A.spmspv([], [], sr)[0]) == 0 and len(A.spmspv(empty, x[empty], sr)[0]) == 0
+
+
+def test_one_expansion_plan_for_both_sparse_products(cbg):
+    """Tile.spmspv (both semirings) and the SelectMax SpMSpV push expand x's columns through the same plan:
+    one list over columns of 1, 255, 256, 257 and 513 stored entries and a column that stores nothing, and
+    lists of one column, give each product's reference and the same units, sum of ceil(len / bound)"""
+    C = cbg.spmv_bounds()[2]
+    assert C == cbg.bfs_bounds()[0]
+    rng = np.random.default_rng(513)
+    m, n = 520, 9
+    lens = {0: 1, 2: 255, 3: 256, 5: 257, 8: 513}  # 1, 4, 6, 7 store nothing
+    rows = [np.sort(rng.choice(m, ln, replace=False)) for ln in lens.values()]
+    cols = [np.full(ln, j) for j, ln in lens.items()]
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    t = hr.from_coo(m, n, rows, cols, cr.pattern_values(rng, "normal", len(rows)))
+    assert cr.column_lengths(t).tolist() == [lens.get(j, 0) for j in range(n)]
+    A = cbg.Tile.from_dict(t)
+    x = rng.uniform(-1, 1, n)
+    for ids in ([0, 2, 3, 4, 5, 8], [8], [3], [4]):
+        ids = np.array(ids, np.int64)
+        units = sum(-(-lens.get(j, 0) // C) for j in ids.tolist())
+        for s, sr in SEMIRINGS:
+            assert_sparse(A.spmspv(ids, x[ids], sr), sv.spmspv(t, ids, x[ids], sr), (ids, s))
+            assert cbg.spmv_stats()["units"] == units, (ids, s)
+        yi, yv = cbg.SpMSpV(A, ids)
+        wi, wv = bfs_ref.spmspv_max(t, ids)
+        assert np.array_equal(yi, wi) and np.array_equal(yv, wv), ids
+        assert cbg.bfs_stats()["push_units"] == units == cbg.spmv_stats()["units"], ids
 
 
 @pytest.mark.parametrize("m", [63, 64, 65])

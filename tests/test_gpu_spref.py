@@ -1,4 +1,4 @@
-"""Sparse indexing on device (csrc/cbg_spref.hip, the grid logic in csrc/cbg_summa.cpp):
+"""Sparse indexing on device (csrc/cbg_spref.hip, the grid logic in csrc/cbg_grid_algos.cpp):
 Tile.spref and SpParMat.SubsRef against the NumPy restatement (tests/spref_ref.py) by bits,
 against the reference's own algorithm run on the device (P * A * Q through the SUMMA), and
 against the reference's results (tests/golden/spref_*.npz); HipMCL with RemoveIsolated and
